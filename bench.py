@@ -19,7 +19,7 @@ per-frame bases, the i64 value column as int32 -- C2's values are in
 the product's hsg_batch_narrow, the pass the decoder (hsg_decode_json_batch)
 runs on every batch it decodes; the library widens them on the device. The
 narrowing runs before the timed region, as decoding does; its host rate is
-reported (input_link.narrowed_by). The same JSON line also carries:
+reported (input_link.narrowed_by). With `--full` the same JSON line also carries:
   hbm_resident  the same steps with the input already resident in HBM
                 (hsg_push_batch on device columns): the kernels' own rate,
                 with the batch pipeline's roofline;
@@ -27,6 +27,20 @@ reported (input_link.narrowed_by). The same JSON line also carries:
                 one row per (record, window) in arrival order, HBM-resident
                 input, its B_alg with the E*O changelog bytes.
 `--input hbm` makes the HBM-resident run the headline (the kernels alone).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+needs: set up, warm up, time the N steps, print the line. The hbm_resident,
+per_record, sql_shape and cpu_baseline blocks take runs of their own and are
+measured only with `--full` (their fields are null otherwise).
+
+`--dump-outputs DIR` writes what the timed path handed over in its last step
+as DIR/<name>.npy (float64): the changelog rows a caller drains -- key_id,
+win_start, win_end, agg0..aggK (src_index too with `--emit per_record`) --
+plus `rows` (their count) and `watermark`. Per-batch rows carry no order of
+their own, so they are written sorted by (key_id, win_start, win_end, integer
+aggregates); per-record rows keep their arrival order. Above 60 MB in all, a
+fixed seeded sample of the (ordered) rows is written. The input is seeded, so
+two builds run with the same arguments can be compared file for file.
 
 Multi-GPU: launched by torch.distributed.run, one process per GPU; every rank
 ingests its own C2-sized slice from host memory (weak scaling) and the library
@@ -73,7 +87,15 @@ def parse():
                    help="emit modes of the sql_shape block")
     p.add_argument("--only-sql", action="store_true",
                    help="profiling aid: only the sql_shape block (HBM-resident), no headline line")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure the hbm_resident, per_record, sql_shape and cpu_baseline blocks "
+                        "(each still has its own --no-* / --cpu-seconds 0 switch)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the last step's changelog rows as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -169,7 +191,9 @@ def main():
     if args.input == "host":
         host_step, host_info = host_steps(op, keys, ts, cols, pieces, spec, emit, world, args)
         elapsed, st0, st1 = timed(host_step, args.warmup, args.steps)
-        if not args.no_hbm:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, host_step, spec, emit, rank, world)
+        if args.full and not args.no_hbm:
             el_h, h0, h1 = timed(dev_step, 1, max(1, args.extra_steps))
             hbm = {"value": round(n_rank * world * max(1, args.extra_steps) / el_h, 1), "unit": "records/s",
                    "steps": max(1, args.extra_steps), "ms_per_step": round(el_h * 1e3 / max(1, args.extra_steps), 3),
@@ -178,6 +202,8 @@ def main():
     else:
         host_info = None
         elapsed, st0, st1 = timed(dev_step, args.warmup, args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dev_step, spec, emit, rank, world)
 
     total_records = n_rank * world * args.steps
     value = total_records / elapsed
@@ -225,7 +251,7 @@ def main():
     per_rec = None
     sql = None
     table_slots, grow_events = int(st1["table_slots"]), int(st1["grow_events"])
-    if world == 1 and not args.force_exchange:
+    if args.full and world == 1 and not args.force_exchange:
         del dev_step
         op.close()
         op = None
@@ -236,7 +262,7 @@ def main():
             sql = sql_shape_block(eng, cfg, keys, ts, cols, pieces, args)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(cfg, spec, args.cpu_seconds)
 
     if rank == 0:
@@ -317,10 +343,13 @@ def device_steps(op, keys, ts, cols, pieces, emit, args):
             if rc != abi.HSG_OK:
                 op._check(rc, "push_batch")
             if emit != abi.HSG_EMIT_NONE:
-                drain_dev()
+                last["rows"] = drain_dev()
         return wm_c.value
 
+    # (--dump-outputs: the columns the last drain filled, its row count, the watermark)
+    last = {"rows": 0}
     step.keep = (descs, outs, drain_dev)
+    step.result = lambda: (outs, last["rows"], wm_c.value)
     return step
 
 
@@ -382,7 +411,7 @@ def host_steps(op, keys, ts, cols, pieces, spec, emit, world, args):
     wpr = -(-spec.size_ms // spec.advance_ms) if spec.window_kind == abi.HSG_HOPPING else 1
     row_bytes = 4 + 8 + 8 + 8 + 8 * len(spec.aggs)
     dev = keys.device
-    state = {"cap": 0, "group": len(descs), "drain": None, "outs": None}
+    state = {"cap": 0, "group": len(descs), "drain": None, "outs": None, "rows": 0}
 
     def plan():
         # rows the library reserves per batch (op_push): n * ranks * wpr (per-batch
@@ -434,9 +463,11 @@ def host_steps(op, keys, ts, cols, pieces, spec, emit, world, args):
             if rc != abi.HSG_OK:
                 op._check(rc, "op_wait")
             if emit != abi.HSG_EMIT_NONE:
-                state["drain"]()
+                state["rows"] = state["drain"]()
 
     step.keep = (descs, host, state)
+    # (--dump-outputs: the columns the last drain filled, its row count, the watermark)
+    step.result = lambda: (state["outs"], state["rows"], wm.value)
     info = {"bytes_per_step": nbytes, "bytes_per_record": round(nbytes / max(1, n_rank), 3),
             "encoding": sorted(encs), "groups": None,
             "narrowed_by": None if args.wide else
@@ -449,6 +480,46 @@ def host_steps(op, keys, ts, cols, pieces, spec, emit, world, args):
                 return -(-len(descs) // state["group"])
             return dict.__getitem__(self, k)
     return step, Info(info)
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # of float64, all files of one rank together
+
+
+def dump_outputs(path, step, spec, emit, rank, world):
+    """--dump-outputs: the rows the timed step's last drain reported (a step
+    whose rows exceed the HBM budget drains in several groups; then the last
+    group's), as one float64 .npy per column. Per-batch rows (one per touched
+    group and batch, in no particular order) are put in a canonical order;
+    per-record rows are in arrival order already. Every value written is an
+    integer below 2^53 or a double, so float64 holds it exactly."""
+    import numpy as np
+    import torch
+    from hstream_amd import abi
+    torch.cuda.synchronize()
+    outs, n, wm = step.result()
+    n = int(n) if emit != abi.HSG_EMIT_NONE else 0
+    names = ["key_id", "win_start", "win_end"] + (["src_index"] if emit == abi.HSG_EMIT_PER_RECORD else [])
+    cols = [(nm, outs[nm][:n]) for nm in names] + [(f"agg{j}", a[:n]) for j, a in enumerate(outs["aggs"])]
+    if n == 0:
+        cols = []
+    sel = None
+    if cols and emit == abi.HSG_EMIT_PER_BATCH:
+        # stable sorts from the least significant key to the most significant
+        sel = torch.arange(n, device=cols[0][1].device)
+        for _, c in reversed([nc for nc in cols if not nc[1].dtype.is_floating_point]):
+            sel = sel[torch.sort(c[sel], stable=True).indices]
+    keep = DUMP_BUDGET_BYTES // (8 * max(1, len(cols)))
+    if n > keep:
+        pick = np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))
+        pick = torch.from_numpy(pick).to(cols[0][1].device)
+        sel = pick if sel is None else sel[pick]
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    for nm, c in cols:
+        c = c if sel is None else c[sel]
+        np.save(os.path.join(path, f"{nm}{suffix}.npy"), c.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(path, f"rows{suffix}.npy"), np.asarray([n], dtype=np.float64))
+    np.save(os.path.join(path, f"watermark{suffix}.npy"), np.asarray([wm], dtype=np.float64))
 
 
 def roofline(st0, st1, spec, emit, valid_bytes=0, form_bytes=0):
@@ -762,7 +833,7 @@ def committed_traffic(args, world):
     with open(paths[-1]) as f:
         d = json.load(f)
     # flags that only switch the extra blocks off measure the same pipeline
-    extra = {"--no-host-input", "--no-per-record", "--no-hbm", "--no-sql-shape", "--input", "hbm"}
+    extra = {"--full", "--no-host-input", "--no-per-record", "--no-hbm", "--no-sql-shape", "--input", "hbm"}
     words = [w for w in d.get("bench_args", "").split() if w not in extra]
     want = ["--config", args.config]
     if pr:

@@ -9,14 +9,14 @@ b() { name=$1; shift; timeout -k 10 500 python bench.py "$@" > gpurun_out/r06/$n
       echo "== $name rc=$rc"; cut -c1-300 gpurun_out/r06/$name.json; return $rc; }
 ARGS="$*"
 run() { n=$1; shift; if [ -z "$ARGS" ] || [[ " $ARGS " == *" $n "* ]]; then b $n "$@" || exit $?; fi; }
-run c2_default --steps 5 --warmup 2 --cpu-seconds 10
-run c2f --config C2f --steps 5 --warmup 2 --cpu-seconds 10 --no-per-record
-run c5 --config C5 --steps 3 --warmup 1 --cpu-seconds 10
-run c3 --config C3 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
-run c4 --config C4 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
-run c3_pr --config C3 --emit per_record --records 100663296 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
-run c4_pr --config C4 --emit per_record --records 167772160 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
-run c2_fx --force-exchange --steps 3 --warmup 1 --cpu-seconds 0 --no-per-record
-run c2_fx_pr --force-exchange --emit per_record --steps 3 --warmup 1 --cpu-seconds 0 --no-per-record
+run c2_default --full --steps 5 --warmup 2 --cpu-seconds 10
+run c2f --full --config C2f --steps 5 --warmup 2 --cpu-seconds 10 --no-per-record
+run c5 --full --config C5 --steps 3 --warmup 1 --cpu-seconds 10
+run c3 --full --config C3 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
+run c4 --full --config C4 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
+run c3_pr --full --config C3 --emit per_record --records 100663296 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
+run c4_pr --full --config C4 --emit per_record --records 167772160 --steps 2 --warmup 1 --cpu-seconds 10 --no-per-record
+run c2_fx --full --force-exchange --steps 3 --warmup 1 --cpu-seconds 0 --no-per-record
+run c2_fx_pr --full --force-exchange --emit per_record --steps 3 --warmup 1 --cpu-seconds 0 --no-per-record
 # the SQL drop-in's op shape (HSG_OPF_LITERAL_FORMS + a LAST passthrough), HBM-resident, both emit modes
-run c2_sql --input hbm --steps 2 --warmup 1 --cpu-seconds 0 --no-per-record --extra-steps 3
+run c2_sql --full --input hbm --steps 2 --warmup 1 --cpu-seconds 0 --no-per-record --extra-steps 3

@@ -65,6 +65,8 @@ struct PartParams {
   int32_t sub;        // partition passes: kPartTileRecs-record sub-tiles per offsets row (one workgroup per row)
   int32_t hold;       // aggregation, general kernels: the worst case (one group per (record, window))
                       // passes `room`: claim nothing, hold back (DevScalars scratch[32] bit 1)
+  int32_t sql_wide;   // the op was created for the SQL lean kernels at 3 - 8 columns or 17 - 24 slots
+                      // (op_device.cpp: sql_lean_eligible then takes those shapes too)
   uint64_t tiles;     // offsets rows of this batch     // partition-pass tiles of this batch
   uint64_t chunk;     // records per aggregation workgroup
   uint64_t room;      // lean path: new groups the table takes this batch (load <= 3/4); past it the
@@ -132,9 +134,10 @@ bool launch_part_agg_lean(hipStream_t s, dim3 g, const Program &prog, const TwPa
                           uint64_t out_base, uint64_t out_cap);
 // The SQL drop-in's op shape (LAST / literal-form slots, k_agg_sql.hip) on
 // packed one-window batches: records with their sequence word, the full slot
-// algebra; false when the shape has no such variant. A batch the kernels
-// cannot finish exactly (a split bucket, an overflowing chunk) leaves
-// DevScalars::scratch[35] set and changes nothing: the careful path runs it.
+// algebra; false when the shape has no such variant. Every packed batch is
+// finished exactly (a split bucket, an overflowing chunk: several partials of
+// a group, combined by k_sql_apply under the row's lock); a batch that is
+// not packed changes nothing and runs on the careful path.
 bool sql_lean_eligible(const Program &prog, const PartParams &pp);
 bool launch_part_agg_sql(hipStream_t s, dim3 g, const Program &prog, const TwParams &p, const PartParams &pp,
                          const TwTable &t, const PartBuffers &pb, DevScalars *sc, const OutCols *out,

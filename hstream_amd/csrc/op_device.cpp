@@ -197,6 +197,21 @@ static void adapt_partitions(OpDevice &d, const hsg_op_config &cfg, const Progra
   d.rbits = d.pane_S ? rb : 0;
 }
 
+// The op shapes the SQL lean kernels take (k_agg_sql.hip sql_lean_eligible):
+// records of one or two columns with programs of at most 16 slots on
+// k_agg_sql, every other width and slot count the engine has on
+// k_agg_sql_wide. HSG_SQL_WIDE_OFF (read when the op is created) keeps an op
+// to the first set, so the second then runs on the record kernels as it did
+// before k_agg_sql_wide: for A/B measurements (tools/sql_wide_ab.py).
+static bool sql_narrow_shape(const hsg_op_config &cfg, const Program &prog) {
+  return (cfg.n_cols == 1 || cfg.n_cols == 2) && prog.n_slots <= 16;
+}
+static bool sql_lean_shape(const hsg_op_config &cfg, const Program &prog) {
+  if (sql_narrow_shape(cfg, prog)) return true;
+  if (getenv("HSG_SQL_WIDE_OFF") != nullptr) return false;
+  return cfg.n_cols >= 1 && cfg.n_cols <= kMaxCols && prog.n_slots <= kMaxSlots;
+}
+
 void wait_table_reset(OpDevice &d) {
   if (!d.reset_pending) return;
   hipStreamWaitEvent(d.stream, d.ev_reset, 0);
@@ -326,15 +341,16 @@ int op_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &prog, u
     rc = perrecord_device_init(d, cfg, prog, err);
     if (rc != HSG_OK) return rc;
   } else if ((cfg.window_kind == HSG_TUMBLING || cfg.window_kind == HSG_UNWINDOWED) && prog_part_seq(prog) &&
-             (cfg.n_cols == 1 || cfg.n_cols == 2) && prog.n_slots <= 16) {
+             sql_lean_shape(cfg, prog)) {
     // the SQL drop-in's op shape (LAST passthroughs, literal forms) of one-window
     // ops: packed records with their sequence word on the SQL lean kernels
-    // (k_agg_sql.hip); a batch they refuse runs on the record kernels
+    // (k_agg_sql.hip); a batch that is not packed runs on the record kernels
     d.use_part = true;
     d.sql_lean = true;
+    d.sql_wide = !sql_narrow_shape(cfg, prog);
     d.pane_S = 1;
-    // no group count before the first batch: the most buckets (a bucket whose
-    // groups overflow its LDS table sends the batch to the careful path)
+    // no group count before the first batch: the most buckets (fewest groups
+    // per LDS table; adapt_partitions sizes them from then on)
     d.np_log2 = kPartMaxLog2;
     rc = part_device_init(d, cfg, prog, err);
     if (rc != HSG_OK) return rc;
@@ -746,9 +762,8 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
   // (device side) from the batch's first keyed record ahead of the optimistic
   // kernels, which then run as on every later batch.
   // the SQL lean kernels (d.sql_lean) run only optimistic packed batches; a
-  // batch they refuse (late records, a wide layout, a split bucket or an
-  // overflowing chunk: scratch[35]) runs again on the record kernels
-  // (k_window.hip k_tw_agg and its LAST / tie resolution pass)
+  // batch that is not one (late records, a wide layout) runs again on the
+  // record kernels (k_window.hip k_tw_agg and its LAST / tie resolution pass)
   const bool sql = d.sql_lean;
   const bool opt = d.use_part && !rec_wm && (!has_last(prog) || sql) && cfg.grace_ms >= 0 &&
                    cfg.window_kind != HSG_SESSION;
@@ -802,6 +817,7 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
       pp.chunk = kAggChunk;
       pp.big = d.agg_big ? 1 : 0;
       pp.defer = 1;
+      pp.sql_wide = d.sql_wide ? 1 : 0;
       const uint64_t lim = d.cap / 8 * d.load8;
       pp.room = lim > d.h_sc->live ? lim - d.h_sc->live : 0;
       pp.hold = !defer_sized && kb.n * d.wpr > pp.room ? 1 : 0;
@@ -823,6 +839,11 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
                       a.pending, d.out_cap, !skipped_wide, &lean);
       if (!lean) skipped_wide = false;  // the general kernel ran both layouts
       skipped_emit = emit_batch && d.pred_direct;  // the lean or the deferred (k_seg_apply) path
+      // (a wide SQL op: not when the batch has more records than its buckets
+      // were sized for -- adapt_partitions: half a chunk each on average --
+      // since buckets then split over workgroups or overflow their LDS
+      // tables, and the changelog comes from the touched list)
+      if (d.sql_wide && kb.n > (pp.chunk << pp.np_log2) / 2) skipped_emit = false;
     } else {
       wait_table_reset(d);
       launch_tw_agg(d.stream, kb, p, d.tw, prog, d.tile_prefix, rec_wm, seq, d.sc, false);
@@ -933,18 +954,10 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
     return rc;
   };
   const uint64_t live0 = d.h_sc->live;  // rows before the batch (after its tw_maintain)
-  // a run of SQL refusals at the most buckets there are (groups beyond what the
-  // LDS tables hold): the careful path directly for a while
-  const bool sql_try = !sql || d.sql_skip == 0;
-  if (!sql_try) d.sql_skip -= 1;
-  int rc = run_room(opt && sql_try);
+  int rc = run_room(opt);
   if (rc != HSG_OK) return rc;
-  const bool sql_refused = sql && opt && sql_try && kb.n && (!d.h_sc->packed || d.h_sc->scratch[35]);
-  // (a refusal is a split bucket or a chunk whose groups overflowed its LDS
-  // table: more buckets for the next batch -- the careful run below leaves no
-  // group count to size them by)
-  const bool sql_ovf = sql_refused && d.h_sc->packed && d.h_sc->scratch[35];
-  const int np_refused = d.np_log2;
+  // (the SQL lean kernels changed nothing: the batch is in the wide layout)
+  const bool sql_refused = sql && opt && kb.n && !d.h_sc->packed;
   if (sql_refused) d.replays += 1;  // (hsg_stats: a lean SQL batch is counted in lean_batches)
   if (opt && kb.n && (d.h_sc->redo || sql_refused)) {
     if (sql) {
@@ -994,12 +1007,6 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
     if (hipEventElapsedTime(&ms, d.ev_a, d.ev_b) == hipSuccess) r.agg_ms = ms;
     r.agg_launches = 1;
     if (d.use_part) adapt_partitions(d, cfg, prog, groups, kb.n);
-    if (sql_ovf) {
-      const int want = np_refused + 1 < kPartMaxLog2 ? np_refused + 1 : kPartMaxLog2;
-      if (d.np_log2 < want) d.np_log2 = want;
-      // already at the most buckets: give the lean SQL kernels a rest
-      if (np_refused >= kPartMaxLog2) d.sql_skip = 16;
-    }
   }
   r.touched = cfg.emit_mode == HSG_EMIT_PER_BATCH ? r.out_rows : d.h_sc->scratch[0];
   return rc;

@@ -77,6 +77,54 @@ HSG_NARROW_ALL = 31
 HSG_OPF_LITERAL_FORMS = 1
 
 
+# hsg_where_opcode: the WHERE program an op runs on the GPU ahead of its aggregate
+HSG_W_COL = 0
+HSG_W_I64 = 1
+HSG_W_F64 = 2
+HSG_W_ADD = 3
+HSG_W_SUB = 4
+HSG_W_MUL = 5
+HSG_W_EQ = 6
+HSG_W_NE = 7
+HSG_W_LT = 8
+HSG_W_GT = 9
+HSG_W_LE = 10
+HSG_W_GE = 11
+HSG_W_BETWEEN = 12
+HSG_W_AND = 13
+HSG_W_OR = 14
+HSG_W_NOT = 15
+HSG_WHERE_MAX_INS = 64
+HSG_WHERE_MAX_DEPTH = 8
+
+
+class hsg_where_imm(C.Union):
+    _fields_ = [("i", C.c_int64), ("f", C.c_double)]
+
+
+class hsg_where_ins(C.Structure):
+    _fields_ = [("op", C.c_int32), ("arg", C.c_int32), ("imm", hsg_where_imm)]
+
+
+def where_ins(op, arg=0):
+    """One instruction: where_ins(HSG_W_COL, c), where_ins(HSG_W_I64, int),
+    where_ins(HSG_W_F64, float), where_ins(HSG_W_ADD) ..."""
+    ins = hsg_where_ins(op=int(op), arg=0)
+    if op == HSG_W_COL:
+        ins.arg = int(arg)
+    elif op == HSG_W_I64:
+        ins.imm.i = int(arg)
+    elif op == HSG_W_F64:
+        ins.imm.f = float(arg)
+    return ins
+
+
+def where_array(program):
+    """A program -- hsg_where_ins, or (op,) / (op, arg) tuples -- as a C array."""
+    items = [p if isinstance(p, hsg_where_ins) else where_ins(*p) for p in program]
+    return (hsg_where_ins * max(1, len(items)))(*items), len(items)
+
+
 class hsg_engine_config(C.Structure):
     _fields_ = [
         ("device", C.c_int32),
@@ -187,6 +235,8 @@ class hsg_stats(C.Structure):
         ("replays", C.c_uint64),
         ("overflow_rows", C.c_uint64),
         ("overflow_rebuilds", C.c_uint64),
+        ("where_dropped", C.c_uint64),
+        ("where_dropped_total", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -200,6 +250,8 @@ EXPORTED_SYMBOLS = [
     "hsg_engine_destroy",
     "hsg_engine_last_error",
     "hsg_op_create",
+    "hsg_where_check",
+    "hsg_op_create_where",
     "hsg_op_destroy",
     "hsg_op_reset",
     "hsg_last_error",

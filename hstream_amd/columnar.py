@@ -29,6 +29,10 @@ class OpSpec:
     state_capacity: int = 0
     out_capacity: int = 0
     flags: int = 0  # HSG_OPF_* (abi.HSG_OPF_LITERAL_FORMS)
+    # WHERE program (abi.hsg_where_ins, or (op[, arg]) tuples) the op runs on the
+    # GPU ahead of the aggregate (hsg_op_create_where); None = no filter.
+    # col_types then lists the columns only the program reads as well.
+    where: Optional[Sequence] = None
 
     @property
     def literal_forms(self) -> bool:

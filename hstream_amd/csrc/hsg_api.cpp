@@ -21,6 +21,7 @@
 
 #include "hsg_internal.h"
 #include "hsg_ops.h"
+#include "hsg_where.h"
 
 using namespace hsg;
 
@@ -168,6 +169,90 @@ int build_program(const hsg_op_config &cfg, const std::vector<int32_t> &col_type
 }
 
 }  // namespace hsg
+
+// ---------------------------------------------------------------------------
+// WHERE program (include/hstream_gpu.h hsg_where_ins): host type check
+// ---------------------------------------------------------------------------
+namespace hsg {
+
+int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, std::string &err) {
+  if (!prog) return fail(err, HSG_E_INVALID, "where: null program");
+  if (n < 1 || n > HSG_WHERE_MAX_INS)
+    return fail(err, HSG_E_INVALID, "where: program length " + std::to_string(n) + " outside 1.." +
+                                        std::to_string(HSG_WHERE_MAX_INS));
+  if (n_cols < 0 || n_cols > kMaxCols || (n_cols > 0 && !col_types))
+    return fail(err, HSG_E_INVALID, "where: bad value columns (max 8)");
+  enum { K_VALUE = 0, K_BOOL = 1 };
+  int kind[HSG_WHERE_MAX_DEPTH];
+  int depth = 0;
+  auto at = [&](int pc) { return "where: instruction " + std::to_string(pc) + ": "; };
+  for (int pc = 0; pc < n; ++pc) {
+    const hsg_where_ins &in = prog[pc];
+    int pops = 0, want = K_VALUE, gives = K_VALUE;
+    switch (in.op) {
+      case HSG_W_COL:
+        if (in.arg < 0 || in.arg >= n_cols)
+          return fail(err, HSG_E_INVALID, at(pc) + "column " + std::to_string(in.arg) + " out of range");
+        if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64)
+          return fail(err, HSG_E_INVALID, at(pc) + "bad column type");
+        break;
+      case HSG_W_I64: break;
+      case HSG_W_F64:
+        if (!(in.imm.f - in.imm.f == 0.0)) return fail(err, HSG_E_INVALID, at(pc) + "f64 constant is not finite");
+        break;
+      case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
+      case HSG_W_EQ: case HSG_W_NE: case HSG_W_LT: case HSG_W_GT: case HSG_W_LE: case HSG_W_GE:
+        pops = 2, gives = K_BOOL;
+        break;
+      case HSG_W_BETWEEN: pops = 3, gives = K_BOOL; break;
+      case HSG_W_AND: case HSG_W_OR: pops = 2, want = K_BOOL, gives = K_BOOL; break;
+      case HSG_W_NOT: pops = 1, want = K_BOOL, gives = K_BOOL; break;
+      default: return fail(err, HSG_E_INVALID, at(pc) + "bad opcode " + std::to_string(in.op));
+    }
+    if (depth < pops) return fail(err, HSG_E_INVALID, at(pc) + "stack underflow");
+    for (int k = 0; k < pops; ++k)
+      if (kind[depth - 1 - k] != want)
+        return fail(err, HSG_E_INVALID,
+                    at(pc) + (want == K_VALUE ? "a bool used as a value" : "a value used as a bool"));
+    depth -= pops;
+    if (depth >= HSG_WHERE_MAX_DEPTH)
+      return fail(err, HSG_E_INVALID, at(pc) + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
+    kind[depth++] = gives;
+  }
+  if (depth != 1)
+    return fail(err, HSG_E_INVALID, "where: " + std::to_string(depth) + " results left on the stack, not one");
+  if (kind[0] != K_BOOL) return fail(err, HSG_E_INVALID, "where: the program leaves a value, not a bool");
+  return HSG_OK;
+}
+
+void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, WhereProg &out) {
+  memset(&out, 0, sizeof(out));
+  out.n = n;
+  for (int c = 0; c < n_cols; ++c)
+    if (col_types[c] == HSG_F64) out.f64 |= 1u << c;
+  for (int pc = 0; pc < n; ++pc) {
+    out.ins[pc] = prog[pc];
+    if (prog[pc].op == HSG_W_COL) out.cols |= 1u << prog[pc].arg;
+  }
+}
+
+}  // namespace hsg
+
+extern "C" int hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, char *err,
+                               size_t err_len) {
+  try {
+    std::string msg;
+    const int rc = where_check(prog, n, col_types, n_cols, msg);
+    if (err && err_len) {
+      const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
+      memcpy(err, msg.data(), k);
+      err[k] = 0;
+    }
+    return rc;
+  } catch (...) {
+    return HSG_E_OOM;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // engine
@@ -406,12 +491,18 @@ uint64_t hsg_windows_per_record(const hsg_op_config &c) {
   return 1;
 }
 
-extern "C" int hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op **out) {
+// hsg_op_create is the n == 0 case.
+extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
+                                   hsg_op **out) {
   try {
     if (!eng || !out) return HSG_E_INVALID;
     *out = nullptr;
     int rc = validate_config(cfg, eng->err);
     if (rc != HSG_OK) return rc;
+    if (n != 0) {
+      rc = where_check(where, n, cfg->col_types, cfg->n_cols, eng->err);
+      if (rc != HSG_OK) return rc;
+    }
     hsg_op *op = new (std::nothrow) hsg_op();
     if (!op) return HSG_E_OOM;
     op->eng = eng;
@@ -424,9 +515,33 @@ extern "C" int hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op *
     memset(&op->stats, 0, sizeof(op->stats));
     // literal forms: extra slots read the literal bit of the valid bytes
     const bool forms = (cfg->flags & HSG_OPF_LITERAL_FORMS) != 0;
-    const std::vector<int32_t> &itypes = op->col_types;
-    const std::vector<hsg_agg> &iaggs = op->aggs;
+    // The kernels' columns. An op with a WHERE program aggregates only the
+    // columns an aggregate reads: a column the program alone reads is part of
+    // the batch (user_cols) and gone once the filter ran (op_device.cpp
+    // stage_batch), so the op is, from there on, the op without it -- the same
+    // slot program, kernel variants and words per record. Ops without a
+    // program keep every column, read or not.
+    std::vector<int32_t> itypes = op->col_types;
+    std::vector<hsg_agg> iaggs = op->aggs;
     op->user_cols = cfg->n_cols;
+    for (int c = 0; c < cfg->n_cols; ++c) op->dev.col_map[c] = c;
+    if (n != 0) {
+      where_compile(where, n, cfg->col_types, cfg->n_cols, op->dev.where);
+      int32_t to_internal[kMaxCols];
+      int ni = 0;
+      itypes.clear();
+      for (int c = 0; c < cfg->n_cols; ++c) {
+        bool read = false;
+        for (const hsg_agg &g : op->aggs) read |= g.kind != HSG_COUNT_ALL && g.column == c;
+        to_internal[c] = read ? ni : -1;
+        if (!read) continue;
+        op->dev.col_map[ni++] = c;
+        itypes.push_back(op->col_types[c]);
+      }
+      for (hsg_agg &g : iaggs)
+        if (g.kind != HSG_COUNT_ALL) g.column = to_internal[g.column];
+      op->cfg.n_cols = ni;
+    }
     rc = build_program(op->cfg, itypes, iaggs, op->prog, eng->err, forms);
     if (rc != HSG_OK) { delete op; return rc; }
     op->dev.user_cols = cfg->n_cols;
@@ -486,6 +601,10 @@ extern "C" int hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op *
   } catch (...) {
     return HSG_E_DEVICE;
   }
+}
+
+extern "C" int hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op **out) {
+  return hsg_op_create_where(eng, cfg, nullptr, 0, out);
 }
 
 extern "C" void hsg_op_destroy(hsg_op *op) {
@@ -570,6 +689,12 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
     args.staged_set = staged_set;
     rc = op_push(op->dev, op->cfg, op->prog, args, res, op->err);
     if (rc != HSG_OK && rc != HSG_E_RANGE && rc != HSG_E_OOM) return rc;
+    if (op->dev.where.n) {
+      // the filter's count came back with the scalars the push fetched
+      const uint64_t seen = op->dev.h_sc->scratch[kWhereWord];
+      res.where_dropped = seen - op->dev.where_seen;
+      op->dev.where_seen = seen;
+    }
     // state was mutated: account for what happened even on OOM / RANGE
     *inout_watermark = res.wm_out;
     op->pending += res.out_rows;
@@ -594,6 +719,8 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
     op->stats.overflow_rows = op->dev.ovf_rows;
     op->stats.overflow_rebuilds = op->dev.ovf_events;
     op->stats.pending_rows = op->pending;
+    op->stats.where_dropped = res.where_dropped;
+    op->stats.where_dropped_total += res.where_dropped;
     op->stats.last_batch_ms = now_ms() - t0;
     op->stats.agg_kernel_ms += res.agg_ms;
     op->stats.agg_kernel_launches += res.agg_launches;

@@ -9,6 +9,7 @@
 #include "hsg_internal.h"
 #include "hsg_part.h"
 #include "hsg_perrecord.h"
+#include "hsg_where.h"
 
 namespace hsg {
 
@@ -80,6 +81,14 @@ struct OpDevice {
   uint64_t batch_cap = 0;       // records this op can take in one push (after exchange)
   int32_t user_cols = 0;        // value columns of the caller's batches (n_cols: the kernels', internal)
   bool forms = false;           // HSG_OPF_LITERAL_FORMS: rows carry literal forms (hsg_rows.form)
+  // WHERE pushdown (k_where.hip): the op's predicate program (where.n == 0:
+  // none), run by stage_batch over the caller's columns; the kernels' column
+  // c is then the caller's col_map[c] (the columns an aggregate reads)
+  WhereProg where = {};
+  int32_t col_map[kMaxCols] = {};
+  const hsg_batch *where_staged = nullptr;  // the batch of this push stage_batch already filtered
+  Batch where_kb = {};                      // ... and what it resolved to
+  uint64_t where_seen = 0;      // the cumulative masked-record count at the last push's end (kWhereWord)
   uint64_t wpr = 1;             // max windows per record
   bool sql_lean = false;        // per-batch LAST / literal-form op on the SQL lean kernels (k_agg_sql.hip)
   bool sql_wide = false;        // ... at 3 - 8 columns or 17 - 24 slots (k_agg_sql_wide.hip; PartParams::sql_wide)
@@ -198,6 +207,7 @@ struct PushResult {
   uint64_t state_rows = 0;
   uint64_t owned = 0;           // records aggregated here after the exchange
   uint64_t global_records = 0;  // records in this batch over all ranks
+  uint64_t where_dropped = 0;   // keyed records of this rank's batch the WHERE program masked
   double agg_ms = 0;
   uint64_t agg_launches = 0;
   double exchange_ms = 0;

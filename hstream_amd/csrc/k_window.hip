@@ -15,6 +15,7 @@
 #include "hsg_dev.h"
 #include "hsg_sort.h"
 #include "hsg_tw.h"
+#include "hsg_where.h"
 
 namespace hsg {
 
@@ -140,7 +141,7 @@ __global__ void k_clear_scalars(DevScalars *sc) {
     sc->packed = 0;
     sc->kbase = 0;
   }
-  if (t < kScratchWords) sc->scratch[t] = 0;
+  if (t < kScratchWords && t != kWhereWord) sc->scratch[t] = 0;  // (kWhereWord: cumulative, hsg_where.h)
 }
 void launch_clear_scalars(hipStream_t s, DevScalars *sc) { hipLaunchKernelGGL(k_clear_scalars, dim3(1), dim3(64), 0, s, sc); }
 
@@ -162,7 +163,7 @@ __global__ void k_fetch_clear_scalars(DevScalars *sc, DevScalars *h) {
     sc->packed = 0;
     sc->kbase = 0;
   }
-  if (t < kScratchWords) sc->scratch[t] = 0;
+  if (t < kScratchWords && t != kWhereWord) sc->scratch[t] = 0;  // (kWhereWord: cumulative, hsg_where.h)
 }
 void launch_fetch_clear_scalars(hipStream_t s, DevScalars *sc, DevScalars *h) {
   hipLaunchKernelGGL(k_fetch_clear_scalars, dim3(1), dim3(64), 0, s, sc, h);

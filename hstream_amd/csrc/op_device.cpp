@@ -223,6 +223,7 @@ int op_device_reset(OpDevice &d, const hsg_op_config &cfg, const Program &prog, 
   memset(d.h_sc, 0, sizeof(DevScalars));  // host mirror (epoch_set gates the optimistic path)
   d.ovf_rows = 0;  // the clear below empties the overflow rows with the regions
   d.sc_clean = false;
+  d.where_seen = 0;
   if (cfg.window_kind == HSG_SESSION) {
     int rc = session_device_reset(d, err);
     if (rc != HSG_OK) return rc;
@@ -294,7 +295,9 @@ int op_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &prog, u
   d.part.text = (uint64_t *)d.tile_max;
   DTRY(dalloc(&d.st_key, d.batch_cap));
   DTRY(dalloc(&d.st_ts, d.batch_cap));
-  for (int c = 0; c < cfg.n_cols; ++c) {
+  // (the caller's columns: an op with a WHERE program stages the columns only
+  // its filter reads too, hsg_api.cpp hsg_op_create_where)
+  for (int c = 0; c < d.user_cols; ++c) {
     DTRY(dalloc(&d.st_col[c], d.batch_cap));
     DTRY(dalloc(&d.st_valid[c], d.batch_cap));
   }
@@ -466,7 +469,7 @@ int op_prestage(OpDevice &d, const hsg_batch *b, int set, std::string &err) {
   if (!s.key) {
     DTRY(dalloc(&s.key, pcap));
     DTRY(dalloc(&s.ts, ts_stage_count<int64_t>(pcap)));
-    for (int c = 0; c < d.n_cols; ++c) {
+    for (int c = 0; c < d.user_cols; ++c) {
       DTRY(dalloc(&s.col[c], pcap));
       DTRY(dalloc(&s.valid[c], pcap));
     }
@@ -533,8 +536,48 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
 // Resolve the batch into device pointers, copying host arrays into staging
 // (or taking the ones op_prestage queued for it). The valid bytes go to the
 // kernels as they are: bit 1 is the literal form the forms slots read.
+//
+// An op with a WHERE program (OpDevice::where) filters here, so every caller
+// -- the synchronous push, prestaged asynchronous batches, the exchange's
+// send sides -- aggregates the masked batch: k_where reads the staged keys
+// and the caller's columns and leaves the key or HSG_KEY_NONE in op-owned
+// memory (in place when the staged keys are the op's own buffer, else in
+// d.st_key: a caller's device-resident array is never written). The kernels'
+// columns are then the ones an aggregate reads (OpDevice::col_map).
 int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
-  return stage_batch_raw(d, b, kb, err, staged_set);
+  // (a sharded push that falls back from the fast exchange stages its batch a
+  // second time: the filter ran, and counted, the first time)
+  if (d.where.n && d.where_staged == b) {
+    kb = d.where_kb;
+    return HSG_OK;
+  }
+  int rc = stage_batch_raw(d, b, kb, err, staged_set);
+  if (rc != HSG_OK || !d.where.n) return rc;
+  if (kb.n) {
+    WhereArgs w;
+    memset(&w, 0, sizeof(w));
+    w.n = kb.n;
+    w.key = kb.key;
+    const bool own = kb.key == d.st_key || (staged_set >= 0 && kb.key == d.pre[staged_set].key);
+    w.out = own ? const_cast<uint32_t *>(kb.key) : d.st_key;
+    for (int c = 0; c < d.user_cols; ++c) {
+      w.col[c] = kb.col[c];
+      w.valid[c] = kb.valid[c];
+    }
+    w.dropped = (unsigned long long *)&d.sc->scratch[kWhereWord];
+    launch_where(d.stream, d.where, w);
+    DTRY(hipGetLastError());
+    kb.key = w.out;
+  }
+  Batch in = kb;
+  for (int c = 0; c < kMaxCols; ++c) {
+    const bool on = c < d.n_cols;
+    kb.col[c] = on ? in.col[d.col_map[c]] : nullptr;
+    kb.valid[c] = on ? in.valid[d.col_map[c]] : nullptr;
+  }
+  d.where_staged = b;
+  d.where_kb = kb;
+  return HSG_OK;
 }
 
 static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
@@ -574,7 +617,7 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
     if (!d.nar_ts) {
       DTRY(dalloc(&d.nar_ts, ts_stage_count<int32_t>(d.batch_cap)));
       DTRY(dalloc(&d.nar_key, d.batch_cap));
-      for (int c = 0; c < d.n_cols; ++c) DTRY(dalloc(&d.nar_col[c], d.batch_cap));
+      for (int c = 0; c < d.user_cols; ++c) DTRY(dalloc(&d.nar_col[c], d.batch_cap));
     }
     const hipMemcpyKind k = hipMemcpyHostToDevice;
     const void *c32[kMaxCols] = {};
@@ -1038,6 +1081,7 @@ static uint64_t table_bound_hint(const OpDevice &d, const hsg_op_config &cfg, co
 int op_push(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const PushArgs &a, PushResult &r,
             std::string &err) {
   const hsg_batch *b = a.batch;
+  d.where_staged = nullptr;  // a new push: stage_batch filters it
   // room in the table for the batch's worst case (sharded ops: in push_local,
   // once the records this rank owns are known)
   if (!a.comm) {

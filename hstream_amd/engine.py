@@ -39,6 +39,10 @@ def load_library(path=LIB_PATH):
     L.hsg_engine_last_error.restype = C.c_char_p
     L.hsg_op_create.argtypes = [vp, P(abi.hsg_op_config), P(vp)]
     L.hsg_op_create.restype = C.c_int
+    L.hsg_where_check.argtypes = [P(abi.hsg_where_ins), C.c_int32, P(C.c_int32), C.c_int32, C.c_char_p, C.c_size_t]
+    L.hsg_where_check.restype = C.c_int
+    L.hsg_op_create_where.argtypes = [vp, P(abi.hsg_op_config), P(abi.hsg_where_ins), C.c_int32, P(vp)]
+    L.hsg_op_create_where.restype = C.c_int
     L.hsg_op_stats.argtypes = [vp, P(abi.hsg_stats)]
     L.hsg_op_stats.restype = C.c_int
     L.hsg_op_set_changelog.argtypes = [vp, P(abi.hsg_rows)]
@@ -72,6 +76,17 @@ class testing_knob:
     def __exit__(self, *exc):
         load_library().hsg_testing_set_knob(self.knob, self.DEFAULTS[self.knob])
         return False
+
+
+def where_check(program, col_types):
+    """hsg_where_check (host only, no GPU): (status, message) for a WHERE
+    program over value columns of the given types."""
+    L = load_library()
+    prog, n = abi.where_array(program)
+    types = (C.c_int32 * max(1, len(col_types)))(*col_types)
+    buf = C.create_string_buffer(256)
+    rc = L.hsg_where_check(prog, n, types, len(col_types), buf, len(buf))
+    return rc, buf.value.decode()
 
 
 def comm_unique_id() -> bytes:
@@ -134,10 +149,16 @@ class GpuOp(OpHandle):
     def __init__(self, engine: Engine, spec: OpSpec):
         cfg, keep = spec.to_config()
         h = C.c_void_p()
-        rc = engine._lib.hsg_op_create(engine._h, C.byref(cfg), C.byref(h))
+        what = "hsg_op_create"
+        if spec.where is not None:
+            what = "hsg_op_create_where"
+            prog, n = abi.where_array(spec.where)
+            rc = engine._lib.hsg_op_create_where(engine._h, C.byref(cfg), prog, n, C.byref(h))
+        else:
+            rc = engine._lib.hsg_op_create(engine._h, C.byref(cfg), C.byref(h))
         if rc != abi.HSG_OK:
             msg = engine._lib.hsg_engine_last_error(engine._h)
-            raise abi.HStreamGpuError(rc, f"hsg_op_create: {msg.decode() if msg else ''}")
+            raise abi.HStreamGpuError(rc, f"{what}: {msg.decode() if msg else ''}")
         self.engine = engine  # keep the engine alive while the op lives
         super().__init__(engine._lib, "hsg", h, spec)
 

@@ -196,6 +196,17 @@ def LAST(f, alias=None, is_float=False):
 
 
 @dataclass
+class Where:
+    """The query's WHERE clause for an aggregate: the refined search condition
+    (hstream_amd.sql RCond*) and which of its fields carry decimals (f64
+    columns). The op runs it on the GPU ahead of the aggregate, where the
+    reference chains genFilterNode in front (Codegen.hs:540)."""
+
+    cond: Any
+    float_fields: Sequence[str] = ()
+
+
+@dataclass
 class Materialized:
     """mKeySerde/mValueSerde/mStateStore (Stream/Internal.hs:123-128): the key
     dictionary plays the key serde, the HBM table the state store."""
@@ -221,8 +232,9 @@ class GroupedStream:
     def sessionWindowedBy(self, windows: SessionWindows) -> "SessionWindowedStream":
         return SessionWindowedStream(self, windows)
 
-    def aggregate(self, aggs: Sequence[Agg], materialized: Materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
-        return Table(self, OpSpec(abi.HSG_UNWINDOWED, emit), aggs, materialized)
+    def aggregate(self, aggs: Sequence[Agg], materialized: Materialized, emit=abi.HSG_EMIT_PER_RECORD,
+                  where: Optional[Where] = None) -> "Table":
+        return Table(self, OpSpec(abi.HSG_UNWINDOWED, emit), aggs, materialized, where)
 
     def count(self, materialized: Materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -237,11 +249,11 @@ class TimeWindowedStream:
         self.grouped = grouped
         self.windows = windows
 
-    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
+    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None) -> "Table":
         w = self.windows
         kind = abi.HSG_TUMBLING if w.twAdvanceMs == w.twSizeMs else abi.HSG_HOPPING
         spec = OpSpec(kind, emit, size_ms=w.twSizeMs, advance_ms=w.twAdvanceMs, grace_ms=w.twGraceMs)
-        return Table(self.grouped, spec, aggs, materialized)
+        return Table(self.grouped, spec, aggs, materialized, where)
 
     def count(self, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -252,9 +264,9 @@ class SessionWindowedStream:
         self.grouped = grouped
         self.windows = windows
 
-    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
+    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None) -> "Table":
         spec = OpSpec(abi.HSG_SESSION, emit, gap_ms=self.windows.swInactivityGap)
-        return Table(self.grouped, spec, aggs, materialized)
+        return Table(self.grouped, spec, aggs, materialized, where)
 
     def count(self, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -267,7 +279,8 @@ class Table:
     (TimeWindowKey | key, {alias: value}) in the order the reference forwards
     them (per-record mode) or one row per touched group (per-batch mode)."""
 
-    def __init__(self, grouped: GroupedStream, spec: OpSpec, aggs: Sequence[Agg], materialized: Materialized):
+    def __init__(self, grouped: GroupedStream, spec: OpSpec, aggs: Sequence[Agg], materialized: Materialized,
+                 where: Optional[Where] = None):
         self.grouped = grouped
         self.aggs = list(aggs)
         self.mat = materialized
@@ -275,12 +288,28 @@ class Table:
         for a in self.aggs:
             if a.kind != abi.HSG_COUNT_ALL and (a.field, a.is_float) not in fields:
                 fields.append((a.field, a.is_float))
-        self.fields = fields
         col_of = {fk: i for i, fk in enumerate(fields)}
         # a column read only by COUNT(col) counts any present value (Codegen.hs:412-422);
         # SUM / MIN / MAX / AVG / LAST need a Number (Codegen.hs:423-461)
         self.numeric = [any(a.kind not in (abi.HSG_COUNT_ALL, abi.HSG_COUNT) and (a.field, a.is_float) == fk
                             for a in self.aggs) for fk in fields]
+        self.where = where
+        if where is not None:
+            # the filter runs in the op (hsg_op_create_where): the fields only it
+            # reads follow the aggregated ones as columns of their own, and every
+            # field it reads must hold a Number (a present non-number drops the
+            # record here, at ingest; the program compares numbers only)
+            from . import sql
+            names = [f for f, _ in fields]
+            for f in sql.where_fields(where.cond):
+                if f in names:
+                    self.numeric[names.index(f)] = True
+                else:
+                    names.append(f)
+                    fields.append((f, f in where.float_fields))
+                    self.numeric.append(True)
+            spec.where = sql.compile_where(where.cond, names, key_field=grouped.key_field)
+        self.fields = fields
         self._decoder = None
         spec.col_types = [abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in fields]
         spec.aggs = [(a.kind, col_of[(a.field, a.is_float)] if a.kind != abi.HSG_COUNT_ALL else 0) for a in self.aggs]

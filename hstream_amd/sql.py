@@ -9,9 +9,19 @@ the BNFC parser/validator are out of scope).
                      operator, the SELECT list the aggregate components.
                      HAVING is not applied to windowed GROUP BY (Codegen.hs:554-559)
                      and only one GROUP BY column exists (Validate.hs:556-562).
+  RExpr* / RCond*    the refined WHERE clause, AST.hs:123-128 and :294-325
+  gen_filter_r       genFilterR, Codegen.hs:303-341 over genRExprValue :290-301,
+                     one record at a time with exact arithmetic: what the
+                     filter means (and the tests' reference)
+  compile_where      the same clause as the postfix program the op runs on
+                     the GPU ahead of the aggregate (include/hstream_gpu.h
+                     hsg_where_ins), where the reference chains genFilterNode
+                     in front of it (Codegen.hs:540)
 """
+import math
 from dataclasses import dataclass
-from typing import List, Optional, Tuple, Union
+from fractions import Fraction
+from typing import Any, List, Optional, Sequence, Tuple, Union
 
 from . import abi, processing as P
 
@@ -64,6 +74,240 @@ class RGroupBy:
     window: Optional[RWindow] = None
 
 
+# ---- WHERE: the refined search condition (AST.hs:123-128, 294-325) ----------
+@dataclass(frozen=True)
+class RExprCol:
+    name: str
+    stream: Optional[str]
+    field: str
+
+
+@dataclass(frozen=True)
+class RExprConst:
+    """constant: an int (ConstantInt) or a float (ConstantNum); a str
+    (ConstantString), bool (ConstantBool) or None (ConstantNull) exists in the
+    reference but is out of the GPU program's scope."""
+    name: str
+    constant: Any
+
+
+@dataclass(frozen=True)
+class RExprBinOp:
+    name: str
+    op: str  # "OpAdd" / "OpSub" / "OpMul"
+    expr1: Any
+    expr2: Any
+
+
+@dataclass(frozen=True)
+class RExprUnaryOp:
+    name: str
+    op: str
+    expr: Any
+
+
+@dataclass(frozen=True)
+class RCondOp:
+    op: str  # "RCompOpEQ" / "RCompOpNE" / "RCompOpLT" / "RCompOpGT" / "RCompOpLEQ" / "RCompOpGEQ"
+    expr1: Any
+    expr2: Any
+
+
+@dataclass(frozen=True)
+class RCondAnd:
+    cond1: Any
+    cond2: Any
+
+
+@dataclass(frozen=True)
+class RCondOr:
+    cond1: Any
+    cond2: Any
+
+
+@dataclass(frozen=True)
+class RCondNot:
+    cond: Any
+
+
+@dataclass(frozen=True)
+class RCondBetween:
+    """expr BETWEEN expr1 AND expr2, in the reference's order (AST.hs:309,317)."""
+    expr1: Any
+    expr: Any
+    expr2: Any
+
+
+RSearchCond = Union[RCondOp, RCondAnd, RCondOr, RCondNot, RCondBetween]
+
+_COMP_OPS = {"RCompOpEQ": abi.HSG_W_EQ, "RCompOpNE": abi.HSG_W_NE, "RCompOpLT": abi.HSG_W_LT,
+             "RCompOpGT": abi.HSG_W_GT, "RCompOpLEQ": abi.HSG_W_LE, "RCompOpGEQ": abi.HSG_W_GE}
+_BIN_OPS = {"OpAdd": abi.HSG_W_ADD, "OpSub": abi.HSG_W_SUB, "OpMul": abi.HSG_W_MUL}
+
+
+def _is_number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float))
+
+
+def _field_name(e: RExprCol) -> str:
+    # composeColName (Internal/Codegen.hs): "stream.field" when the stream is named
+    return e.field if e.stream is None else f"{e.stream}.{e.field}"
+
+
+def _expr_value(e, value):
+    """genRExprValue over a JSON object: the Number as an exact Fraction (a
+    Scientific); raises KeyError for a missing field (getFieldByName,
+    Internal/Codegen.hs:41-49) and TypeError for what binOpOnValue /
+    compareValue have no case for."""
+    if isinstance(e, RExprCol):
+        name = _field_name(e)
+        if name not in value:
+            raise KeyError(f"Key {name!r} is not found in object")
+        v = value[name]
+        if not _is_number(v):
+            raise TypeError(f"field {name!r} is not a Number")
+        return Fraction(v)
+    if isinstance(e, RExprConst):
+        if not _is_number(e.constant):
+            raise TypeError("constant is not a Number")
+        return Fraction(e.constant)
+    if isinstance(e, RExprBinOp):
+        a, b = _expr_value(e.expr1, value), _expr_value(e.expr2, value)
+        if e.op == "OpAdd":
+            return a + b
+        if e.op == "OpSub":
+            return a - b
+        if e.op == "OpMul":
+            return a * b
+    raise TypeError(f"unsupported expression {e!r}")
+
+
+def gen_filter_r(cond, value) -> bool:
+    """genFilterR (Codegen.hs:303-341) for one record's value object. Python
+    evaluates as eagerly as Haskell evaluates lazily here: `or` / `and` look at
+    the right side only when the left one did not decide, BETWEEN looks at its
+    upper bound only when lower <= expr held, and every comparison needs both
+    of its sides. Raises (KeyError) where the reference throws: the caller
+    drops the record, as runTask does (Processor.hs:140-143)."""
+    if cond is None:
+        return True  # RWhereEmpty
+    if isinstance(cond, RCondOp):
+        a, b = _expr_value(cond.expr1, value), _expr_value(cond.expr2, value)
+        return {"RCompOpEQ": a == b, "RCompOpNE": a != b, "RCompOpLT": a < b, "RCompOpGT": a > b,
+                "RCompOpLEQ": a <= b, "RCompOpGEQ": a >= b}[cond.op]
+    if isinstance(cond, RCondOr):
+        return gen_filter_r(cond.cond1, value) or gen_filter_r(cond.cond2, value)
+    if isinstance(cond, RCondAnd):
+        return gen_filter_r(cond.cond1, value) and gen_filter_r(cond.cond2, value)
+    if isinstance(cond, RCondNot):
+        return not gen_filter_r(cond.cond, value)
+    if isinstance(cond, RCondBetween):
+        lo, x = _expr_value(cond.expr1, value), _expr_value(cond.expr, value)
+        if lo > x:
+            return False
+        return not x > _expr_value(cond.expr2, value)
+    raise TypeError(f"unsupported condition {cond!r}")
+
+
+def where_fields(cond) -> List[str]:
+    """The fields a condition reads, in first-use order."""
+    out: List[str] = []
+
+    def walk(n):
+        if isinstance(n, RExprCol):
+            if _field_name(n) not in out:
+                out.append(_field_name(n))
+        elif isinstance(n, (RExprBinOp, RCondOp)):
+            walk(n.expr1), walk(n.expr2)
+        elif isinstance(n, RExprUnaryOp):
+            walk(n.expr)
+        elif isinstance(n, (RCondAnd, RCondOr)):
+            walk(n.cond1), walk(n.cond2)
+        elif isinstance(n, RCondNot):
+            walk(n.cond)
+        elif isinstance(n, RCondBetween):
+            walk(n.expr1), walk(n.expr), walk(n.expr2)
+
+    walk(cond)
+    return out
+
+
+def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None) -> List[Tuple]:
+    """The condition as a postfix hsg_where_ins program, [(op,) | (op, arg)],
+    over value columns named `fields` (column c = fields[c]). ValueError for
+    what the program cannot say -- string / bool / null constants, a predicate
+    on the group key, the reference's unary functions, a non-finite constant, a
+    program past HSG_WHERE_MAX_INS or HSG_WHERE_MAX_DEPTH: such a WHERE stays
+    upstream of the op (genFilterNode)."""
+    fields = list(fields)
+    prog: List[Tuple] = []
+
+    def expr(e) -> int:  # emits e, returns the stack depth it needs
+        if isinstance(e, RExprCol):
+            name = _field_name(e)
+            if key_field is not None and name == key_field:
+                raise ValueError(f"WHERE on the group key {name!r} is not pushed down")
+            if name not in fields:
+                raise ValueError(f"WHERE reads {name!r}, which is not a value column")
+            prog.append((abi.HSG_W_COL, fields.index(name)))
+            return 1
+        if isinstance(e, RExprConst):
+            c = e.constant
+            if not _is_number(c):
+                raise ValueError(f"constant {c!r} is not a number: not pushed down")
+            if isinstance(c, int):
+                if not -2**63 <= c < 2**63:
+                    raise ValueError(f"integer constant {c} does not fit an i64")
+                prog.append((abi.HSG_W_I64, c))
+            else:
+                if not math.isfinite(c):
+                    raise ValueError("non-finite constant")
+                prog.append((abi.HSG_W_F64, c))
+            return 1
+        if isinstance(e, RExprBinOp):
+            if e.op not in _BIN_OPS:
+                raise ValueError(f"operator {e.op} is not pushed down")
+            d1 = expr(e.expr1)
+            d2 = expr(e.expr2)
+            prog.append((_BIN_OPS[e.op],))
+            return max(d1, 1 + d2)
+        if isinstance(e, RExprUnaryOp):
+            raise ValueError(f"unary function {e.op} is not pushed down")
+        raise ValueError(f"unsupported expression {e!r}")
+
+    def search(c) -> int:
+        if isinstance(c, RCondOp):
+            if c.op not in _COMP_OPS:
+                raise ValueError(f"bad comparison {c.op}")
+            d1 = expr(c.expr1)
+            d2 = expr(c.expr2)
+            prog.append((_COMP_OPS[c.op],))
+            return max(d1, 1 + d2)
+        if isinstance(c, (RCondAnd, RCondOr)):
+            d1 = search(c.cond1)
+            d2 = search(c.cond2)
+            prog.append((abi.HSG_W_AND if isinstance(c, RCondAnd) else abi.HSG_W_OR,))
+            return max(d1, 1 + d2)
+        if isinstance(c, RCondNot):
+            d = search(c.cond)
+            prog.append((abi.HSG_W_NOT,))
+            return d
+        if isinstance(c, RCondBetween):
+            d1 = expr(c.expr1)
+            d2 = expr(c.expr)
+            d3 = expr(c.expr2)
+            prog.append((abi.HSG_W_BETWEEN,))
+            return max(d1, 1 + d2, 2 + d3)
+        raise ValueError(f"unsupported condition {c!r}")
+
+    depth = search(cond)
+    if len(prog) > abi.HSG_WHERE_MAX_INS:
+        raise ValueError(f"WHERE needs {len(prog)} instructions (max {abi.HSG_WHERE_MAX_INS})")
+    if depth > abi.HSG_WHERE_MAX_DEPTH:
+        raise ValueError(f"WHERE needs a stack of {depth} (max {abi.HSG_WHERE_MAX_DEPTH})")
+    return prog
+
+
 # SELECT items: ("COUNT(*)",) / ("COUNT", col) / ("SUM", col) / ("MIN", col) /
 # ("MAX", col) / ("AVG", col) / ("COL", col); optional alias as last element.
 SelItem = Tuple
@@ -102,19 +346,27 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=()) -> List[P.Agg]
 
 
 def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.HSG_EMIT_PER_RECORD,
-                      float_fields=(), state_capacity=0) -> P.Table:
-    """genGroupByNode: groupBy -> (timeWindowedBy | sessionWindowedBy)? -> aggregate."""
+                      float_fields=(), state_capacity=0, where=None) -> P.Table:
+    """genGroupByNode: groupBy -> (timeWindowedBy | sessionWindowedBy)? -> aggregate.
+    where: the query's RSearchCond, run by the op on the GPU where the
+    reference chains genFilterNode in front (Codegen.hs:540); ValueError when
+    compile_where cannot express it (the caller then filters upstream)."""
     grouped = P.groupBy(engine, group_by.column)
     aggs = gen_aggregate_components(sel, float_fields)
     mat = P.Materialized(state_capacity=state_capacity)
+    if where is not None:
+        where = P.Where(where, float_fields)
     w = group_by.window
     if w is None:
-        return grouped.aggregate(aggs, mat, emit)
+        return grouped.aggregate(aggs, mat, emit, where=where)
     if isinstance(w, RTumblingWindow):
-        return grouped.timeWindowedBy(P.mkTumblingWindow(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit)
+        return grouped.timeWindowedBy(P.mkTumblingWindow(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit,
+                                                                                               where=where)
     if isinstance(w, RHoppingWindow):
         return grouped.timeWindowedBy(
-            P.mkHoppingWindow(diff_time_to_ms(w.length), diff_time_to_ms(w.hop))).aggregate(aggs, mat, emit)
+            P.mkHoppingWindow(diff_time_to_ms(w.length), diff_time_to_ms(w.hop))).aggregate(aggs, mat, emit,
+                                                                                            where=where)
     if isinstance(w, RSessionWindow):
-        return grouped.sessionWindowedBy(P.mkSessionWindows(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit)
+        return grouped.sessionWindowedBy(P.mkSessionWindows(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit,
+                                                                                                 where=where)
     raise ValueError("bad window")

@@ -121,6 +121,48 @@ enum hsg_enc {
 };
 #define HSG_TS16_FRAME 4096
 
+/* WHERE pushdown: the query's filter as a postfix program the op runs on the
+ * GPU over each staged batch, ahead of the aggregate. The reference runs it as
+ * a node of its own in front of the aggregate (genFilterNode whr s0,
+ * hstream-sql/src/HStream/SQL/Codegen.hs:540) with the semantics of
+ * genRExprValue / genFilterR (Codegen.hs:290-341); a record it drops -- or one
+ * whose field lookup throws (getFieldByName, Internal/Codegen.hs:41-49) -- has
+ * already moved stream time (Processor.hs:139-143), which here is: its key
+ * becomes HSG_KEY_NONE. Nothing is compacted, so src_index keeps its meaning.
+ *
+ * A value is an i64 or an f64, typed statically by its column's type or its
+ * constant's kind. ADD / SUB / MUL of two i64 is an i64 and wraps; with an f64
+ * operand the result is an f64. An i64 is compared with an f64 exactly, as
+ * Scientific values compare (2^53 + 1 > 9007199254740992.0): never through a
+ * conversion of the integer to double. Evaluation is three-valued (true /
+ * false / error), which is what Haskell's laziness makes of a missing field:
+ *   COL        error when bit 0 of the record's valid byte is 0 (bit 1, the
+ *              literal form, is not looked at)
+ *   ADD..MUL   error if either operand is
+ *   EQ..GE     error if either operand is
+ *   BETWEEN    (lo x hi): error if lo or x is; else false if lo > x, whatever
+ *              hi is; else error if hi is; else x <= hi
+ *   OR         l true -> true; l error -> error; l false -> r
+ *   AND        l false -> false; l error -> error; l true -> r
+ *   NOT        NOT error = error
+ * A record is kept only when the result is true. Both operands of AND / OR
+ * are always computed (nothing has a side effect): the short circuit is a
+ * rule on values. Not expressible, such a WHERE stays upstream of the op:
+ * string / bool / null constants, predicates on the group key, the
+ * reference's unary functions. */
+enum hsg_where_opcode {
+  HSG_W_COL = 0,  /* push value column `arg`                                  */
+  HSG_W_I64 = 1,  /* push imm.i                                               */
+  HSG_W_F64 = 2,  /* push imm.f (finite)                                      */
+  HSG_W_ADD = 3, HSG_W_SUB = 4, HSG_W_MUL = 5,        /* value value -> value */
+  HSG_W_EQ = 6, HSG_W_NE = 7, HSG_W_LT = 8, HSG_W_GT = 9, HSG_W_LE = 10, HSG_W_GE = 11, /* value value -> bool */
+  HSG_W_BETWEEN = 12,                                  /* lo x hi -> bool      */
+  HSG_W_AND = 13, HSG_W_OR = 14, HSG_W_NOT = 15        /* bool (bool) -> bool  */
+};
+typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } hsg_where_ins;
+#define HSG_WHERE_MAX_INS   64
+#define HSG_WHERE_MAX_DEPTH 8
+
 typedef struct hsg_engine hsg_engine;
 typedef struct hsg_op hsg_op;
 
@@ -267,6 +309,9 @@ typedef struct {
                                  many open windows); the next batch rebuilds the table    */
   uint64_t overflow_rebuilds; /* table rebuilds (twice the slots, twice the region size)
                                  that overflow rows caused                               */
+  uint64_t where_dropped;     /* records of the last batch (this rank's ingest) that arrived
+                                 keyed and were masked by the op's WHERE program          */
+  uint64_t where_dropped_total;
 } hsg_stats;
 
 /* Completion callback of hsg_push_batch_async: rc is what hsg_push_batch
@@ -284,6 +329,24 @@ const char *hsg_engine_last_error(const hsg_engine *eng);
 
 /* ---- operator: one per windowed GROUP BY -------------------------------------- */
 int  hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op **out);
+/* Type-check a WHERE program against an op's value columns; pure host code
+ * (no GPU). HSG_OK only when every operand has the kind its instruction takes
+ * (value or bool), the stack never holds more than HSG_WHERE_MAX_DEPTH
+ * entries, exactly one bool is left at the end, every column is in range,
+ * 1 <= n <= HSG_WHERE_MAX_INS and every f64 constant is finite; else
+ * HSG_E_INVALID with a message in err (NUL-terminated, cut to err_len). */
+int  hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, char *err,
+                     size_t err_len);
+/* hsg_op_create with a WHERE program of n instructions (n == 0: none; that is
+ * hsg_op_create). Every batch then carries cfg->n_cols columns as before: the
+ * ones the aggregates read and the ones only the program reads, which leave
+ * the batch once the filter ran (the op aggregates as the op without them
+ * would). The program is copied and fixed for the op's life; hsg_op_reset
+ * keeps it. A program hsg_where_check refuses fails the creation with
+ * HSG_E_INVALID and that message in hsg_engine_last_error. Collective on a
+ * sharded engine, like hsg_op_create. */
+int  hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *prog, int32_t n,
+                         hsg_op **out);
 void hsg_op_destroy(hsg_op *op);
 int  hsg_op_reset(hsg_op *op);            /* drop all state and pending rows          */
 const char *hsg_last_error(const hsg_op *op);

@@ -83,6 +83,16 @@ __device__ inline int64_t slot_identity_dev(int32_t op) {
   }
 }
 
+// Element of a present f64 for a MIN / MAX slot of a group that starts from
+// its first record's element instead of an identity row (the session merge
+// path's point sessions): the fold's initial value maxBound / minBound
+// (Codegen.hs:438,451) lies inside the f64 range, and a value beyond it never
+// replaces it. Not for ops with tie words (there the bound has a word of its own).
+__device__ inline int64_t f64_extreme_elem(int op, double d) {
+  const uint64_t o = f64_ord(d), id = (uint64_t)slot_identity_dev(op);
+  return (int64_t)(op == S_MIN_F ? (o < id ? o : id) : (o > id ? o : id));
+}
+
 __device__ inline bool rec_present(const Batch &b, int c, uint64_t i) {
   return b.valid[c] == nullptr || b.valid[c][i] != 0;
 }

@@ -247,9 +247,12 @@ __device__ __host__ inline int log2_exact(uint32_t g) {  // -1 unless g is a pow
   return l;
 }
 
-// Order-preserving map f64 -> u64 (total order on non-NaN values).
+// Order-preserving map f64 -> u64 (total order on non-NaN values). -0.0 maps
+// to +0.0's image: the two are one value to the reference (a Scientific has no
+// negative zero), so a MIN / MAX reached by both is a tie for the tie words.
 __device__ __host__ inline uint64_t f64_ord(double d) {
   uint64_t u = __builtin_bit_cast(uint64_t, d);
+  if (u == 0x8000000000000000ull) u = 0;
   return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
 __device__ __host__ inline double f64_unord(uint64_t o) {

@@ -1031,8 +1031,8 @@ __device__ __attribute__((always_inline)) inline void ss_vw_elem(const PV &prog,
     const int64_t x = (int64_t)v[1 + c];
     switch (op) {
       case S_CNT: e[s] = 1; break;
-      case S_MIN_F:
-      case S_MAX_F: e[s] = (int64_t)f64_ord(__builtin_bit_cast(double, x)); break;
+      case S_MIN_F:  // (a record is a point session of its own here: no identity row to fold into)
+      case S_MAX_F: e[s] = f64_extreme_elem(op, __builtin_bit_cast(double, x)); break;
       default: e[s] = x; break;
     }
   }

@@ -222,3 +222,49 @@ def test_decoder_batches_equal_full_width(eng, name):
     rows_equal(g.dump_state(), o.dump_state(), f64, what=f"{name} decoder state")
     g.close()
     o.close()
+
+
+@pytest.mark.parametrize("mode", ["sync", "device"])
+def test_narrow_extremes_widen_exactly(eng, mode):
+    """The ends of the narrow encodings: HSG_ENC_I32 columns holding INT32_MIN,
+    INT32_MAX, -1 and 0; HSG_ENC_DEC32 at scales 0, 1, 9 and 18 (a batch each)
+    with mantissas INT32_MIN, INT32_MAX and +-1, whose value is the double
+    nearest m / 10^scale. MIN / MAX / LAST / COUNT of both columns, equal with
+    no tolerance to the oracle fed the widened arrays."""
+    import torch
+    from decimal import Decimal
+    aggs = [(abi.HSG_COUNT_ALL, 0), (abi.HSG_MIN, 0), (abi.HSG_MAX, 0), (abi.HSG_LAST, 0), (abi.HSG_COUNT, 1),
+            (abi.HSG_MIN, 1), (abi.HSG_MAX, 1), (abi.HSG_LAST, 1)]
+    spec = OpSpec(abi.HSG_TUMBLING, abi.HSG_EMIT_PER_BATCH, size_ms=10_000, col_types=[abi.HSG_I64, abi.HSG_F64],
+                  aggs=aggs)
+    g, o = eng.op(spec), pyoracle.OracleOp(spec)
+    f64 = spec.agg_is_f64()
+    exact = list(f64)  # every f64 output is a MIN / MAX / LAST
+    i32 = np.array([-2**31, 2**31 - 1, -1, 0], np.int32)
+    man = np.array([-2**31, 2**31 - 1, 1, -1], np.int32)
+    n = 64
+    rng = np.random.default_rng(17)
+    wm_g = wm_o = -1
+    for b, scale in enumerate((0, 1, 9, 18)):
+        key = rng.integers(0, 24, size=n).astype(np.uint32)  # ~3 records per key: some groups see one value only
+        ts = (3_000_000 + 10_000 * b + np.sort(rng.integers(0, 10_000, size=n))).astype(np.int64)
+        c0 = i32[rng.integers(0, 4, size=n)]
+        c1 = man[rng.integers(0, 4, size=n)]
+        wide1 = np.array([float(Decimal(int(m)).scaleb(-scale)) for m in c1], np.float64)
+        valid = [(rng.random(n) >= 0.1).astype(np.uint8) for _ in range(2)]
+        t32 = (ts - int(ts.min())).astype(np.int32)
+        kw = dict(ts_base=int(ts.min()), col_enc=[abi.HSG_ENC_I32, abi.HSG_ENC_DEC32], col_scale=[0, scale])
+        wm_o = o.push(key, ts, [c0.astype(np.int64), wide1], valid, watermark=wm_o)
+        if mode == "sync":
+            wm_g = g.push(key, t32, [c0, c1], valid, watermark=wm_g, **kw)
+        else:
+            d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+            dv = [d(v) for v in valid]
+            torch.cuda.synchronize()
+            wm_g = g.push(d(key.view(np.int32)), d(t32), [d(c0), d(c1)], dv, watermark=wm_g,
+                          mem=abi.HSG_MEM_DEVICE, **kw)
+        assert wm_g == wm_o, f"scale {scale}: watermark"
+        rows_equal(g.drain(), o.drain(), f64, what=f"{mode} scale {scale}", exact_f64=exact)
+    rows_equal(g.dump_state(), o.dump_state(), f64, what=f"{mode} state", exact_f64=exact)
+    g.close()
+    o.close()

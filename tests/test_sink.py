@@ -500,3 +500,211 @@ def test_sink_literal_forms_and_key_spellings(case):
     sink.close()
     op.close()
     eng.close()
+
+
+# ---------------------------------------------------------------------------
+# GPU: the device build of the number formatter (hsg_fmt.h under k_sink.hip:
+# __umul64hi where the host takes __int128, the 128-bit multiplies compiled
+# for gfx950) over the whole value domain. Sink.encode takes host rows of any
+# content, so the rows are built by hand: every f64 output of a row holds the
+# same double, every i64 output the same integer.
+# ---------------------------------------------------------------------------
+def _domain_doubles():
+    import valgen
+    rng = random.Random(5)  # test_f64_text_random_bits' seed
+    vals = [struct.unpack("<d", struct.pack("<Q", rng.getrandbits(64)))[0] for _ in range(20000)]
+    rng = random.Random(6)  # test_f64_text_decimal_like_values' set
+    vals += [round(rng.uniform(-1e7, 1e7), rng.randrange(0, 7)) for _ in range(20000)]
+    vals += [m * 10.0 ** k for k in range(-30, 30) for m in (1, 3, 7, 9, 5)]
+    vals += [float(v) for v in valgen.F64_EXTREMES] + [valgen.SUBNORMAL_UNIT * k for k in (1, 2, 4096, -3)]
+    vals += [float(v) for v in valgen.I64_SPECIALS[:8]] + [2.0 ** 53 + 2.0, 1e22, 1e23, 5e-324, float("nan"),
+                                                          float("inf"), float("-inf")]
+    return np.array(vals, np.float64)
+
+
+def _domain_ints():
+    import valgen
+    return np.array([0, 1, -1, 42, -(1 << 63), (1 << 63) - 1, 10 ** 18, -10 ** 18 + 7]  # test_int64_text's list
+                    + valgen.I64_SPECIALS + valgen.I64_BIG_SPECIALS + valgen.I64_EXTREMES
+                    + valgen.I64_CROSSING_CYCLE + [10 ** k for k in range(19)] + [-(10 ** k) for k in range(19)]
+                    + [123456789012345678, -9000000000000000000, 1000000000000000001], np.int64)
+
+
+_D_AGGS = [(abi.HSG_COUNT_ALL, 0), (abi.HSG_SUM, 0), (abi.HSG_MIN, 0), (abi.HSG_MAX, 0), (abi.HSG_SUM, 1),
+           (abi.HSG_MIN, 1), (abi.HSG_MAX, 1), (abi.HSG_LAST, 1), (abi.HSG_AVG, 1)]
+_D_MEMBERS = [("cnt", 0), ("isum", 1), ("imin", 2), ("imax", 3), ("k", -1), ("fsum", 4), ("fmin", 5), ("fmax", 6),
+              ("flast", 7), ("favg", 8)]
+_D_KIND = {abi.HSG_SUM: "sum", abi.HSG_MIN: "min", abi.HSG_MAX: "max"}
+
+
+def _domain_sink(forms):
+    import torch
+    assert torch.cuda.is_available()
+    from hstream_amd.columnar import OpSpec
+    from hstream_amd.engine import Engine
+    from hstream_amd.ingest import KeyDict
+    from hstream_amd.sink import Sink
+    eng = Engine(device=0, batch_capacity=1 << 10)
+    spec = OpSpec(abi.HSG_TUMBLING, abi.HSG_EMIT_PER_BATCH, size_ms=5000, col_types=[abi.HSG_I64, abi.HSG_F64],
+                  aggs=_D_AGGS, flags=abi.HSG_OPF_LITERAL_FORMS if forms else 0)
+    op = eng.op(spec)
+    keys = KeyDict()
+    kids = [keys.encode(k) for k in (1, "a\"b", 2.5)]
+    sink = Sink(op, keys, "k", _D_MEMBERS, windowed=True)
+    return eng, op, keys, kids, sink, spec
+
+
+def _domain_rows(kids, ints, doubles, form=None):
+    from hstream_amd.columnar import Rows
+    n = len(doubles)
+    iv = ints[np.arange(n) % len(ints)]
+    aggs = [iv.copy() if j < 4 else doubles.copy() for j in range(len(_D_AGGS))]
+    return Rows(np.array(kids, np.uint32)[np.arange(n) % len(kids)], (np.arange(n, dtype=np.int64) % 7) * 5000,
+                (np.arange(n, dtype=np.int64) % 7) * 5000 + 5000, np.full(n, -1, np.int64), aggs, form)
+
+
+def _domain_compare(got, rows, keys, text_of):
+    written = [_D_MEMBERS[m] for m in aeson_member_order([a for a, _ in _D_MEMBERS])]
+    assert len(got) == len(rows) > 0
+    ktexts = {}
+    for i, (kb, vb) in enumerate(got):
+        kid = int(rows.key_id[i])
+        ktext = ktexts.setdefault(kid, keys.text(kid))
+        mem = [(alias, ktext if j < 0 else text_of(i, j)) for alias, j in written]
+        ek, ev = _ref_record(ktext, "k", int(rows.win_start[i]), mem, True)
+        assert kb == ek, (i, kb, ek)
+        assert vb == ev, (i, float(rows.aggs[4][i]), int(rows.aggs[1][i]), vb, ev)
+
+
+@pytest.mark.gpu
+def test_sink_device_formatter_whole_domain():
+    """Rows without literal forms: 20 000 random-bit doubles, the decimal-like
+    set, the valgen specials (identities of SUM / MIN / MAX among them, which
+    print as the reference's integer initial values in that aggregate's
+    member only), NaN / inf; int64 members over the int64 specials. Value and
+    key bytes against ref_f64 / str, byte for byte."""
+    eng, op, keys, kids, sink, spec = _domain_sink(False)
+    rows = _domain_rows(kids, _domain_ints(), _domain_doubles())
+    f64 = spec.agg_is_f64()
+
+    def text_of(i, j):
+        v = rows.aggs[j][i]
+        return ref_f64(float(v), _D_KIND.get(_D_AGGS[j][0], "")) if f64[j] else str(int(v))
+
+    _domain_compare(sink.encode(rows), rows, keys, text_of)
+    sink.close()
+    op.close()
+    eng.close()
+
+
+def _integral_doubles():
+    rng = random.Random(8)
+    vals = [2.0 ** 63, -(2.0 ** 63), float(np.nextafter(2.0 ** 63, np.inf)), float(np.nextafter(-(2.0 ** 63), -np.inf)),
+            float(np.nextafter(2.0 ** 63, 0.0)), 1e19, -1e19, 2.0 ** 64, 1e22, 1e23, 1e100, 1e300, -1e300,
+            1.7976931348623157e308, -1.7976931348623157e308, 0.0, -0.0, 1.0, -1.0, 2.0 ** 53, 2.0 ** 53 + 2.0,
+            2.0 ** 62, -(2.0 ** 62), 4.0e15, 123456789.0]
+    for _ in range(4000):  # any double from 2^53 up is integral: random mantissas, exponents 2^53 .. 2^1023
+        bits = (rng.getrandbits(1) << 63) | (rng.randrange(1023 + 53, 2047) << 52) | rng.getrandbits(52)
+        vals.append(struct.unpack("<d", struct.pack("<Q", bits))[0])
+    vals += [float(rng.randrange(-10 ** 15, 10 ** 15)) for _ in range(1000)]
+    return np.array(vals, np.float64)
+
+
+def _integral_text(v: float) -> str:
+    """An integral f64 Scientific with exponent >= 0: below 2^63 the exact
+    integer, from 2^63 up the shortest round-trip digits followed by zeros."""
+    return str(int(v)) if abs(v) < 2.0 ** 63 else str(int(Decimal(repr(v))))
+
+
+@pytest.mark.gpu
+def test_sink_device_formatter_literal_forms():
+    """Rows with literal forms (hsg_rows.form, two bits per output: bit 0 the
+    value prints as an integer, bit 1 the aggregate's initial value). One
+    encode call each: (a) integral-form doubles up to 1.7976931348623157e308
+    (fmt_f64_integral, the kNumTextIntMax buffer) with integral int64s; (b)
+    form bits 0, every value in Generic form (an int64 as "6.0":
+    fmt_i64_decimal), and identity rows for SUM / MIN / MAX whatever the slot
+    holds."""
+    import valgen
+    eng, op, keys, kids, sink, spec = _domain_sink(True)
+    f64 = spec.agg_is_f64()
+    formed = [j for j, (k, _c) in enumerate(_D_AGGS) if k in (abi.HSG_SUM, abi.HSG_MIN, abi.HSG_MAX, abi.HSG_LAST)]
+    word = lambda bits: sum(bits << (2 * j) for j in formed)
+    ints = _domain_ints()
+    # (a) every formed output integral
+    dbl = _integral_doubles()
+    rows = _domain_rows(kids, ints, dbl, np.full(len(dbl), word(1), np.uint32))
+
+    def text_a(i, j):
+        v = rows.aggs[j][i]
+        if j not in formed:
+            return ref_f64(float(v)) if f64[j] else str(int(v))
+        return _integral_text(float(v)) if f64[j] else str(int(v))
+
+    _domain_compare(sink.encode(rows), rows, keys, text_a)
+    # (b) Generic forms, and every third row the initial values
+    dbl = np.concatenate([_domain_doubles()[::7], np.array([float(v) for v in valgen.F64_EXTREMES])])
+    form = np.where(np.arange(len(dbl)) % 3 == 2, word(3), word(0)).astype(np.uint32)
+    rows = _domain_rows(kids, ints, dbl, form)
+    initial = {abi.HSG_SUM: "0", abi.HSG_MIN: str((1 << 63) - 1), abi.HSG_MAX: str(-(1 << 63)), abi.HSG_LAST: "0"}
+
+    def text_b(i, j):
+        v = rows.aggs[j][i]
+        if j not in formed:
+            return ref_f64(float(v)) if f64[j] else str(int(v))
+        if form[i]:
+            return initial[_D_AGGS[j][0]]
+        return ref_f64(float(v)) if f64[j] else generic(Decimal(int(v)))
+
+    _domain_compare(sink.encode(rows), rows, keys, text_b)
+    sink.close()
+    op.close()
+    eng.close()
+
+
+@pytest.mark.gpu
+def test_sink_negative_zero_sum_with_forms():
+    """An f64 SUM that is exactly -0.0 can only come from "-0.0" literals
+    alone; -0.0 is also the slot's identity bit pattern. With literal forms
+    the row knows a decimal literal reached the SUM and prints "0.0" as the
+    reference does (a Scientific has no negative zero); MIN / MAX / LAST of
+    such a group likewise. Without forms it prints "0": DESIGN.md section 9."""
+    import torch
+    assert torch.cuda.is_available()
+    from hstream_amd.columnar import OpSpec
+    from hstream_amd.engine import Engine
+    from hstream_amd.ingest import Decoder, KeyDict, pack_records
+    from hstream_amd.sink import Sink
+    comps = [("cnt", "cnt", None), ("sum_x", "sum", "x"), ("min_x", "min", "x"), ("max_x", "max", "x"),
+             ("last_x", "last", "x")]
+    kinds = {"cnt": abi.HSG_COUNT_ALL, "sum": abi.HSG_SUM, "min": abi.HSG_MIN, "max": abi.HSG_MAX, "last": abi.HSG_LAST}
+    # key 1: only "-0.0"; key 2: "-0.0" and "0" (the SUM turns +0.0, decimal); key 3: no x at all (initial values)
+    lits = [("1", "-0.0"), ("2", "-0.0"), ("1", "-0.0"), ("3", None), ("2", "0"), ("1", "-0.0"), ("2", "-0.0")]
+    recs = [(k, 1_000_000 + 10 * i, {"x": x}) for i, (k, x) in enumerate(lits)]
+    vals = [('{"k":' + k + ("" if v["x"] is None else ',"x":' + v["x"]) + "}").encode() for k, _t, v in recs]
+    eng = Engine(device=0, batch_capacity=1 << 10)
+    spec = OpSpec(abi.HSG_TUMBLING, abi.HSG_EMIT_PER_BATCH, size_ms=5000, col_types=[abi.HSG_F64],
+                  aggs=[(kinds[k], 0) for _a, k, _c in comps], flags=abi.HSG_OPF_LITERAL_FORMS)
+    op = eng.op(spec)
+    keys = KeyDict()
+    dec = Decoder("k", [("x", abi.HSG_F64, True)], literal_forms=True)
+    members = [(a, j) for j, (a, _k, _c) in enumerate(comps)] + [("k", -1)]
+    sink = Sink(op, keys, "k", members, windowed=True)
+    written = [members[m] for m in aeson_member_order([a for a, _ in members])]
+    ref = _ref_literal_rows(recs, comps, ("tumbling", 5000), abi.HSG_EMIT_PER_BATCH, [len(recs)])[0]
+    assert {x[1]: x[3]["sum_x"] for x in ref} == {"1": "0.0", "2": "0.0", "3": "0"}  # the restatement itself
+    buf, off = pack_records(vals)
+    kid, tb, cs, valid, _st, rej, _sp = dec.decode(keys, buf, off, np.array([t for _k, t, _v in recs], np.int64),
+                                                   spellings=True)
+    assert rej == 0
+    assert np.signbit(cs[0][0]) and cs[0][0] == 0.0  # the decoder keeps the literal's sign: the slot really holds -0.0
+    op.push(kid, tb, cs, valid, watermark=-1)
+    got = sorted(sink.encode(op.drain()))
+    exp = []
+    for _r, ktext, ws, texts in ref:
+        own = _first_text(ktext)
+        exp.append(_ref_record(own, "k", ws, [(a, own if j < 0 else texts[a]) for a, j in written], True))
+    assert got == sorted(exp), (got, sorted(exp))
+    sink.close()
+    op.close()
+    eng.close()

@@ -60,8 +60,12 @@ def gen_small(seed, n, nkeys, col_types=(abi.HSG_I64,), late_frac=0.02, neg_frac
     return key, ts, cols, valid
 
 
-def rows_equal(a: Rows, b: Rows, agg_f64, ordered=False, what=""):
-    """Bit-exact keys/windows/integer aggregates; f64 within F64_RTOL."""
+def rows_equal(a: Rows, b: Rows, agg_f64, ordered=False, what="", exact_f64=None, rtol=F64_RTOL, atol=0.0):
+    """Bit-exact keys/windows/integer aggregates; f64 within F64_RTOL.
+    exact_f64: per aggregate, True = an f64 output that must be numerically
+    equal with no tolerance (MIN / MAX / LAST); the other f64 outputs within
+    rtol (<= F64_RTOL) and atol."""
+    assert rtol <= F64_RTOL
     if not ordered:
         a, b = a.sorted(), b.sorted()
     assert len(a) == len(b), f"{what}: row count {len(a)} != {len(b)}"
@@ -72,8 +76,8 @@ def rows_equal(a: Rows, b: Rows, agg_f64, ordered=False, what=""):
         np.testing.assert_array_equal(a.src_index, b.src_index, err_msg=f"{what}: src_index")
     for j, f in enumerate(agg_f64):
         x, y = a.aggs[j], b.aggs[j]
-        if f:
-            np.testing.assert_allclose(x, y, rtol=F64_RTOL, atol=0, equal_nan=True, err_msg=f"{what}: agg {j}")
+        if f and not (exact_f64 is not None and exact_f64[j]):
+            np.testing.assert_allclose(x, y, rtol=rtol, atol=atol, equal_nan=True, err_msg=f"{what}: agg {j}")
         else:
             np.testing.assert_array_equal(x, y, err_msg=f"{what}: agg {j}")
 

@@ -3,9 +3,6 @@
 // k_agg_s{2,4,6,8}.hip so the variants compile in parallel. Not ABI.
 #pragma once
 
-#include <initializer_list>
-#include <type_traits>
-
 #include "hsg_dev.h"
 #include "hsg_part.h"
 #include "hsg_tw.h"
@@ -13,107 +10,8 @@
 namespace hsg {
 
 // ---------------------------------------------------------------------------
-// Slot-program views
-// ---------------------------------------------------------------------------
-// The per-record LDS update dispatches on every slot's op. Read from the
-// runtime Program (ProgRT) that dispatch is a scalar branch chain per slot and
-// record; a program signature baked into the kernel (ProgSig<SIG>) folds it
-// to the slot's one LDS atomic. SIG packs 7 bits per slot, slot 0 lowest:
-// (op + 1) in the low 4 bits, the column in the high 3; 0 ends the program.
-struct ProgRT {
-  const Program &p;
-  __device__ explicit ProgRT(const Program &q) : p(q) {}
-  __device__ int n() const { return p.n_slots; }
-  __device__ int op(int s) const { return p.slot_op[s]; }
-  __device__ int col(int s) const { return p.slot_col[s]; }
-};
-
-template <uint64_t SIG, uint64_t SIG2 = 0>
-struct ProgSig {
-  // slot s's 7-bit code: slots 0..8 in SIG, 9..17 in SIG2 (programs of more
-  // than 9 slots: the SQL drop-in's shape, literal forms and a passthrough)
-  static constexpr uint32_t code(int s) {
-    return s < 9 ? (uint32_t)((SIG >> (7 * s)) & 127u) : (uint32_t)((SIG2 >> (7 * (s - 9))) & 127u);
-  }
-  static constexpr int count() {
-    int k = 0;
-    while (k < 18 && (code(k) & 15u) != 0) ++k;
-    return k;
-  }
-  static constexpr int op_of(int s) { return (int)(code(s) & 15u) - 1; }
-  static constexpr int col_of(int s) { return (int)((code(s) >> 4) & 7u); }
-  // the MIN / MAX slot a tie-word slot breaks ties of (build_program: the
-  // one MIN (MAX) slot over the same column)
-  static constexpr int aux_of(int s) {
-    const int want = op_of(s) == S_TIE_MIN ? 0 : 1;
-    for (int k = 0; k < count(); ++k) {
-      const int o = op_of(k);
-      const bool mn = o == S_MIN_I || o == S_MIN_F, mx = o == S_MAX_I || o == S_MAX_F;
-      if (((want == 0 && mn) || (want == 1 && mx)) && col_of(k) == col_of(s)) return k;
-    }
-    return 0;
-  }
-  // the LAST_FORM slot over the column of LAST_SEQ slot s (-1: none): its
-  // word is (seq + 1) << 1 | bit over the same present records, so the
-  // LAST_SEQ slot is that word >> 1 and needs no update of its own
-  static constexpr int last_form_of(int s) {
-    for (int k = 0; k < count(); ++k)
-      if (op_of(k) == S_LAST_FORM && col_of(k) == col_of(s)) return k;
-    return -1;
-  }
-  static constexpr bool has_ties() {
-    for (int k = 0; k < count(); ++k)
-      if (op_of(k) == S_TIE_MIN || op_of(k) == S_TIE_MAX) return true;
-    return false;
-  }
-  __device__ ProgSig() {}
-  __device__ explicit ProgSig(const Program &) {}
-  __device__ constexpr int n() const { return count(); }
-  __device__ constexpr int op(int s) const { return op_of(s); }
-  __device__ constexpr int col(int s) const { return col_of(s); }
-};
-
-template <uint64_t SIG, uint64_t SIG2 = 0>
-using ProgView = typename std::conditional<SIG == 0, ProgRT, ProgSig<SIG, SIG2>>::type;
-
-// tie-word helpers over either view
-__device__ inline int pv_aux(const ProgRT &pv, int s) { return pv.p.slot_aux[s]; }
-__device__ inline bool pv_ties(const ProgRT &pv) { return pv.p.ties != 0; }
-template <uint64_t SIG, uint64_t SIG2>
-__device__ constexpr int pv_aux(const ProgSig<SIG, SIG2> &, int s) { return ProgSig<SIG, SIG2>::aux_of(s); }
-template <uint64_t SIG, uint64_t SIG2>
-__device__ constexpr bool pv_ties(const ProgSig<SIG, SIG2> &) { return ProgSig<SIG, SIG2>::has_ties(); }
-__device__ inline int pv_last_form(const ProgRT &, int) { return -1; }
-template <uint64_t SIG, uint64_t SIG2>
-__device__ constexpr int pv_last_form(const ProgSig<SIG, SIG2> &, int s) { return ProgSig<SIG, SIG2>::last_form_of(s); }
-
-// signature of a runtime program (0: not expressible); slots past the ninth
-// go to *sig2 when it is given (else such a program has no signature)
-inline uint64_t program_sig(const Program &p, uint64_t *sig2 = nullptr) {
-  if (p.n_slots > (sig2 ? 18 : 8)) return 0;
-  uint64_t sig = 0, hi = 0;
-  for (int s = 0; s < p.n_slots; ++s) {
-    if (p.slot_op[s] < 0 || p.slot_op[s] > 14 || p.slot_col[s] < 0 || p.slot_col[s] > 7) return 0;
-    // (a tie word's MIN / MAX slot is implied: the one over its column)
-    if (slot_is_tie(p.slot_op[s])) {
-      const int v = p.slot_aux[s], vo = p.slot_op[v];
-      const bool ok = p.slot_col[v] == p.slot_col[s] &&
-                      (p.slot_op[s] == S_TIE_MIN ? (vo == S_MIN_I || vo == S_MIN_F) : (vo == S_MAX_I || vo == S_MAX_F));
-      if (!ok) return 0;
-    }
-    const uint64_t c = (uint64_t)((p.slot_op[s] + 1) | (p.slot_col[s] << 4));
-    if (s < 9) sig |= c << (7 * s);
-    else hi |= c << (7 * (s - 9));
-  }
-  if (sig2) *sig2 = hi;
-  return sig;
-}
-
-// ---------------------------------------------------------------------------
 // LDS aggregation of one chunk
 // ---------------------------------------------------------------------------
-// One partitioned record held in registers: [w0 w1 col 0..C-1 seq+1?]. Runtime
-// word selection is an unrolled compare chain, so the record never leaves VGPRs.
 // One partitioned record held in registers, in its memory layout (PK: packed,
 // see hsg_part.h). Runtime word selection is an unrolled compare chain, so
 // the record never leaves VGPRs.
@@ -141,7 +39,12 @@ struct PRec {
   __device__ bool dec(int c) const { return ((uint64_t)word(CB + C) >> (56 + c)) & 1ull; }
 };
 
-// contribution of the record to slot s (identity when absent)
+// contribution of the record to slot s (identity when absent; LAST_VAL, which
+// no caller reads, 0). A local form of rec_elem (hsg_slots.h), as are the
+// switches of lds_apply and flush_row_atomic below and PRec's own decodes:
+// k_part_agg is at the edge of its register budget (128 VGPRs), and over the
+// shared routines its runtime-program variants gain scratch (fan-out 8-slot:
+// 232 -> 296 B).
 template <class PG, typename R>
 __device__ inline int64_t prec_elem(const PG &prog, int s, const R &r) {
   const int op = prog.op(s);
@@ -868,12 +771,6 @@ static void agg_launch_pk(hipStream_t s, dim3 g, bool maybe_packed, const Progra
 // Aggregate sets with a kernel specialised on their slot program (ProgSig):
 // the SQL aggregates over one numeric column that a windowed GROUP BY most
 // often asks for. Every other program runs the runtime-program kernel.
-constexpr uint64_t sig_ops(std::initializer_list<int> ops) {
-  uint64_t sig = 0;
-  int k = 0;
-  for (int op : ops) sig |= (uint64_t)(op + 1) << (7 * k++);
-  return sig;
-}
 // COUNT(*), SUM, AVG, MIN, MAX of an i64 / f64 column
 constexpr uint64_t kSigAllI = sig_ops({S_CNT_ALL, S_SUM_I, S_CNT, S_MIN_I, S_MAX_I});
 constexpr uint64_t kSigAllF = sig_ops({S_CNT_ALL, S_SUM_F, S_CNT, S_MIN_F, S_MAX_F});
@@ -886,15 +783,6 @@ constexpr uint64_t kSigSumMaxI = sig_ops({S_SUM_I, S_MAX_I});
 // MAX(v)` with literal forms (build_program's slot order): the passthrough's
 // LAST pair and form, COUNT(*), SUM and its decimal count, COUNT(v), MIN / MAX
 // with their tie words -- eleven slots, the last two in the second word
-constexpr uint64_t sig_ops_at(std::initializer_list<int> ops, int first) {
-  uint64_t sig = 0;
-  int k = 0;
-  for (int op : ops) {
-    if (k >= first && k < first + 9) sig |= (uint64_t)(op + 1) << (7 * (k - first));
-    ++k;
-  }
-  return sig;
-}
 #define HSG_SQL_C2_OPS(SUM, MIN, MAX) \
   {S_LAST_SEQ, S_LAST_VAL, S_LAST_FORM, S_CNT_ALL, SUM, S_CNT_DEC, S_CNT, MIN, S_TIE_MIN, MAX, S_TIE_MAX}
 constexpr uint64_t kSigSqlI = sig_ops_at(HSG_SQL_C2_OPS(S_SUM_I, S_MIN_I, S_MAX_I), 0);

@@ -1,8 +1,11 @@
-// Device helpers shared by the gfx950 kernels (wave64 scans / reductions, the
-// aggregate-slot algebra, output conversion). Not part of the ABI.
+// Device helpers shared by the gfx950 kernels (wave64 scans / reductions,
+// output conversion; the aggregate-slot algebra is hsg_slots.h). Not part of
+// the ABI.
 #pragma once
 
 #include "hsg_internal.h"
+#include "hsg_part.h"
+#include "hsg_slots.h"
 
 namespace hsg {
 
@@ -71,36 +74,6 @@ __device__ inline void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-__device__ inline int64_t slot_identity_dev(int32_t op) {
-  switch (op) {
-    case S_MIN_I: return INT64_MAX;
-    case S_MAX_I: return INT64_MIN;
-    case S_MIN_F: return (int64_t)f64_ord(9223372036854775807.0);
-    case S_MAX_F: return (int64_t)f64_ord(-9223372036854775808.0);
-    case S_SUM_F: return INT64_MIN;  // -0.0 (slot_identity)
-    case S_TIE_MIN: return 1;        // seq 0, integral: the initial maxBound
-    default: return 0;
-  }
-}
-
-// Element of a present f64 for a MIN / MAX slot of a group that starts from
-// its first record's element instead of an identity row (the session merge
-// path's point sessions): the fold's initial value maxBound / minBound
-// (Codegen.hs:438,451) lies inside the f64 range, and a value beyond it never
-// replaces it. Not for ops with tie words (there the bound has a word of its own).
-__device__ inline int64_t f64_extreme_elem(int op, double d) {
-  const uint64_t o = f64_ord(d), id = (uint64_t)slot_identity_dev(op);
-  return (int64_t)(op == S_MIN_F ? (o < id ? o : id) : (o > id ? o : id));
-}
-
-__device__ inline bool rec_present(const Batch &b, int c, uint64_t i) {
-  return b.valid[c] == nullptr || b.valid[c][i] != 0;
-}
-// the value's JSON literal prints in Generic form (bit 1 of its valid byte,
-// hstream_ingest.h literal_forms)
-__device__ inline bool rec_decimal(const Batch &b, int c, uint64_t i) {
-  return b.valid[c] != nullptr && (b.valid[c][i] & 2u) != 0;
-}
 // a form slot's word for a present record: (seq + 1) << 1 | integral literal
 __device__ inline int64_t form_word(const Batch &b, int c, uint64_t i, uint64_t seq1) {
   return (int64_t)((seq1 << 1) | (rec_decimal(b, c, i) ? 0u : 1u));
@@ -109,133 +82,12 @@ __device__ inline int64_t form_word(const Batch &b, int c, uint64_t i, uint64_t 
 // Sequence word of a partitioned record of an op with LAST / literal-form
 // slots (hsg_part.h): (global seq + 1) in the low 56 bits, bit 56 + c set when
 // column c's literal is decimal (bit 1 of its valid byte).
-constexpr uint64_t kSeqMask = (1ull << 56) - 1;
 __device__ inline uint64_t seq_word(const Batch &b, int C, int has_valid, int64_t seq, uint64_t i) {
   uint64_t w = (uint64_t)(seq + 1) & kSeqMask;
   if (has_valid)
     for (int c = 0; c < C && c < 8; ++c)
       if (b.valid[c] && (b.valid[c][i] & 2u)) w |= 1ull << (56 + c);
   return w;
-}
-
-// Contribution of record i to state slot s (identity when the field is absent).
-__device__ inline int64_t slot_elem(const Program &prog, int s, const Batch &b, uint64_t i, uint64_t seq1) {
-  const int op = prog.slot_op[s];
-  const int c = prog.slot_col[s];
-  if (op == S_CNT_ALL) return 1;
-  if (op == S_LAST_VAL) {
-    // paired with the preceding LAST_SEQ slot; value only meaningful when present
-    return rec_present(b, c, i) ? b.col[c][i] : 0;
-  }
-  if (!rec_present(b, c, i)) return slot_identity_dev(op);
-  switch (op) {
-    case S_CNT: return 1;
-    case S_SUM_I:
-    case S_SUM_F:
-    case S_MIN_I:
-    case S_MAX_I: return b.col[c][i];
-    case S_MIN_F:
-    case S_MAX_F: return (int64_t)f64_ord(__builtin_bit_cast(double, b.col[c][i]));
-    case S_LAST_SEQ: return (int64_t)seq1;
-    case S_CNT_DEC: return rec_decimal(b, c, i) ? 1 : 0;
-    case S_TIE_MIN:
-    case S_TIE_MAX:
-    case S_LAST_FORM: return form_word(b, c, i, seq1);
-    default: return 0;
-  }
-}
-
-// a <- a (+) e for one slot, where e comes later in arrival order than a.
-// LAST_SEQ/LAST_VAL are combined as a pair by the caller (see combine_row).
-__device__ inline int64_t slot_combine(int op, int64_t a, int64_t e) {
-  switch (op) {
-    case S_CNT_ALL:
-    case S_CNT:
-    case S_SUM_I: return (int64_t)((uint64_t)a + (uint64_t)e);
-    case S_SUM_F: return __builtin_bit_cast(int64_t, __builtin_bit_cast(double, a) + __builtin_bit_cast(double, e));
-    case S_MIN_I: return e < a ? e : a;
-    case S_MAX_I: return e > a ? e : a;
-    case S_MIN_F: return (uint64_t)e < (uint64_t)a ? e : a;
-    case S_MAX_F: return (uint64_t)e > (uint64_t)a ? e : a;
-    case S_CNT_DEC: return (int64_t)((uint64_t)a + (uint64_t)e);
-    case S_LAST_FORM: return (uint64_t)e > (uint64_t)a ? e : a;
-    default: return a;  // S_TIE_*: combined with their MIN / MAX slot (tie_combine)
-  }
-}
-
-// "e is better than a" for the MIN / MAX slot op vop (equal: a tie)
-__device__ inline bool extreme_better(int vop, int64_t e, int64_t a) {
-  switch (vop) {
-    case S_MIN_I: return e < a;
-    case S_MAX_I: return e > a;
-    case S_MIN_F: return (uint64_t)e < (uint64_t)a;
-    case S_MAX_F: return (uint64_t)e > (uint64_t)a;
-    default: return false;
-  }
-}
-// tie word after a <- a (+) e, from the MIN / MAX values before the combine
-// (va, ve): the better value's word; on a tie the earlier literal for MIN
-// (min n x = n) and the later for MAX (max n x = x) -- by record sequence, so
-// any grouping of a record fold gives the sequential fold's word
-__device__ inline int64_t tie_combine(int op, int vop, int64_t va, int64_t ve, int64_t ta, int64_t te) {
-  if (extreme_better(vop, ve, va)) return te;
-  if (va != ve) return ta;
-  if (op == S_TIE_MIN) return (uint64_t)te < (uint64_t)ta ? te : ta;
-  return (uint64_t)te > (uint64_t)ta ? te : ta;
-}
-
-// Row-wise combine over MS compile-time-bounded slots (registers, no scratch).
-// the value of slot v of a register row (v not a compile-time index)
-template <int MS>
-__device__ inline int64_t reg_at(const int64_t (&r)[MS], int v) {
-  int64_t x = 0;
-#pragma unroll
-  for (int s = 0; s < MS; ++s)
-    if (s == v) x = r[s];
-  return x;
-}
-
-// tie words first, against the MIN / MAX values before the combine
-template <int MS>
-__device__ inline void combine_ties(const Program &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    if (s >= prog.n_slots) break;
-    const int op = prog.slot_op[s];
-    if (!slot_is_tie(op)) continue;
-    const int v = prog.slot_aux[s];
-    a[s] = tie_combine(op, prog.slot_op[v], reg_at<MS>(a, v), reg_at<MS>(e, v), a[s], e[s]);
-  }
-}
-
-template <int MS>
-__device__ inline void combine_row(const Program &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
-  if (prog.ties) combine_ties<MS>(prog, a, e);
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    if (s >= prog.n_slots) break;
-    const int op = prog.slot_op[s];
-    if (op == S_LAST_SEQ) {
-      if (e[s] != 0) {
-        a[s] = e[s];
-        if (s + 1 < MS) a[s + 1] = e[s + 1];
-      }
-    } else if (op != S_LAST_VAL) {
-      a[s] = slot_combine(op, a[s], e[s]);
-    }
-  }
-}
-
-template <int MS>
-__device__ inline void identity_row(const Program &prog, int64_t (&a)[MS]) {
-#pragma unroll
-  for (int s = 0; s < MS; ++s) a[s] = s < prog.n_slots ? slot_identity_dev(prog.slot_op[s]) : 0;
-}
-
-template <int MS>
-__device__ inline void elem_row(const Program &prog, int64_t (&e)[MS], const Batch &b, uint64_t i, uint64_t seq1) {
-#pragma unroll
-  for (int s = 0; s < MS; ++s) e[s] = s < prog.n_slots ? slot_elem(prog, s, b, i, seq1) : 0;
 }
 
 __device__ inline int64_t out_value_w(const Program &prog, int j, int64_t a, int64_t bcnt) {
@@ -302,34 +154,6 @@ __device__ inline uint32_t out_form_reg(const Program &prog, const int64_t (&r)[
   for (int j = 0; j < prog.n_out; ++j)
     if (prog.form_kind[j] != F_NONE) f |= form_bits_w(prog.form_kind[j], reg_at<MS>(r, prog.form_a[j])) << (2 * j);
   return f;
-}
-
-// Session merge, acc <- sessionMergeF rk acc cur (SessionWindowedStream.hs
-// :100-114; acc = the new record with the sessions merged so far, cur = the
-// next overlapped session in end order): the aggregate components'
-// aggregateMergeF (Codegen.hs:409-469) -- counts and sums add, MIN / MAX keep
-// the extreme with min n1 n2 / max n1 n2 on ties (n1 = acc's literal for
-// MIN, n2 = cur's for MAX), passthrough columns take cur's (o2)
-template <int MS>
-__device__ inline void merge_row(const Program &prog, int64_t (&acc)[MS], const int64_t (&cur)[MS]) {
-  if (prog.ties) {
-#pragma unroll
-    for (int s = 0; s < MS; ++s) {
-      if (s >= prog.n_slots) break;
-      const int op = prog.slot_op[s];
-      if (!slot_is_tie(op)) continue;
-      const int v = prog.slot_aux[s], vop = prog.slot_op[v];
-      const int64_t va = reg_at<MS>(acc, v), vc = reg_at<MS>(cur, v);
-      if (extreme_better(vop, vc, va) || (va == vc && op == S_TIE_MAX)) acc[s] = cur[s];
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    if (s >= prog.n_slots) break;
-    const int op = prog.slot_op[s];
-    if (op == S_LAST_SEQ || op == S_LAST_VAL || op == S_LAST_FORM) acc[s] = cur[s];
-    else acc[s] = slot_combine(op, acc[s], cur[s]);
-  }
 }
 
 // Per-record stream time for the records of one tile (record (r, thread) =

@@ -36,7 +36,7 @@ enum SlotOp : int32_t {
   S_LAST_FORM = 13, // max over (seq + 1) << 1 | integral literal of present records (LAST's form)
 };
 
-__host__ __device__ inline bool slot_is_form(int32_t op) { return op >= S_CNT_DEC && op <= S_LAST_FORM; }
+__host__ __device__ constexpr bool slot_is_form(int32_t op) { return op >= S_CNT_DEC && op <= S_LAST_FORM; }
 __host__ __device__ inline bool slot_is_tie(int32_t op) { return op == S_TIE_MIN || op == S_TIE_MAX; }
 
 // Output column j = f(slot a [, slot b]).

@@ -20,6 +20,24 @@ constexpr int kMaxSeg = 8;                            // deferred flush segments
 // Packed layout (optimistic batches whose windows span < 2^16 advances, C <= 8,
 // nwin < 256): words - 1 words, the first one
 //   [key | (krel - kbase) << 32 | nwin << 48 | valid bits << 56]
+// The sequence word (hsg_dev.h seq_word) is seq + 1 in its low 56 bits and
+// column c's decimal-literal flag at bit 56 + c.
+// The decodes, for every holder of such a record (pk: packed; w0, w1: its
+// first two words, w1 unread when packed; sw: its sequence word):
+constexpr uint64_t kSeqMask = (1ull << 56) - 1;
+__host__ __device__ inline uint32_t part_key(uint64_t w0) { return (uint32_t)w0; }
+__host__ __device__ inline uint32_t part_krel(bool pk, uint64_t w0, uint32_t kbase) {
+  return pk ? kbase + (uint32_t)((w0 >> 32) & 0xFFFFull) : (uint32_t)(w0 >> 32);
+}
+__host__ __device__ inline uint32_t part_nwin(bool pk, uint64_t w0, uint64_t w1) {
+  return pk ? (uint32_t)((w0 >> 48) & 0xFFull) : (uint32_t)w1;
+}
+__host__ __device__ inline bool part_present(bool pk, uint64_t w0, uint64_t w1, int c) {
+  return pk ? (w0 >> (56 + c)) & 1ull : (w1 >> (32 + c)) & 1ull;
+}
+__host__ __device__ inline int64_t seqw_seq1(uint64_t sw) { return (int64_t)(sw & kSeqMask); }
+__host__ __device__ inline bool seqw_dec(uint64_t sw, int c) { return (sw >> (56 + c)) & 1ull; }
+
 struct PartBuffers {
   uint32_t *hist;         // [tiles][np] tile-major per-tile bucket counts
   uint32_t *offt;         // [tiles][np] tile-major bucket-major-order offsets of each (tile, bucket) run

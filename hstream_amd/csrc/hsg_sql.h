@@ -216,7 +216,9 @@ __device__ inline void sql_phase2(const PV &pv, int64_t *__restrict__ agg, const
 
 // one record's contribution to every slot, as a partial of its own (a record
 // whose group found no room in the chunk's LDS table): the state of a group
-// holding only this record
+// holding only this record. A local form of rec_elems (hsg_slots.h) with the
+// COUNT(col) mask inside: over rec_elems and a mask pass k_agg_sql gains
+// scratch (its 8-slot runtime-program variants 0 -> 144 / 176 B).
 template <int MS, class PV, class R>
 __device__ inline void sql_elems(const PV &pv, const R &r, uint32_t skip, int64_t (&v)[MS]) {
 #pragma unroll
@@ -527,44 +529,11 @@ __device__ inline int64_t sql_claim_lds(const TwTable &t, uint64_t g, uint32_t *
   return tw_ovf_claim(t, g, fresh);  // the region's sub-table is full
 }
 
-// combine_row for the 24-slot class: the same algebra, the slot loops unrolled
-// by the front end (at 24 slots the optimizer leaves hsg_dev.h's loops
-// rolled, which puts the rows they index in scratch)
-template <int MS, int S = 0>
-__device__ inline void sql_combine_ties_u(const Program &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
-  if constexpr (S < MS) {
-    if (S < prog.n_slots && slot_is_tie(prog.slot_op[S])) {
-      const int v = prog.slot_aux[S];
-      a[S] = tie_combine(prog.slot_op[S], prog.slot_op[v], reg_at<MS>(a, v), reg_at<MS>(e, v), a[S], e[S]);
-    }
-    sql_combine_ties_u<MS, S + 1>(prog, a, e);
-  }
-}
-template <int MS, int S = 0>
-__device__ inline void sql_combine_row_u(const Program &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
-  if constexpr (S < MS) {
-    if (S < prog.n_slots) {
-      const int op = prog.slot_op[S];
-      if (op == S_LAST_SEQ) {
-        if (e[S] != 0) {
-          a[S] = e[S];
-          if constexpr (S + 1 < MS) a[S + 1] = e[S + 1];
-        }
-      } else if (op != S_LAST_VAL) {
-        a[S] = slot_combine(op, a[S], e[S]);
-      }
-    }
-    sql_combine_row_u<MS, S + 1>(prog, a, e);
-  }
-}
+// combine_row; the 24-slot class takes the front-end-unrolled form
 template <int MS>
 __device__ inline void sql_combine_row(const Program &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
-  if constexpr (MS > 16) {
-    if (prog.ties) sql_combine_ties_u<MS>(prog, a, e);
-    sql_combine_row_u<MS>(prog, a, e);
-  } else {
-    combine_row<MS>(prog, a, e);
-  }
+  if constexpr (MS > 16) combine_row_u<MS>(prog, a, e);
+  else combine_row<MS>(prog, a, e);
 }
 
 // a <- a (+) e in any order: combine_row with the LAST pair kept by sequence
@@ -805,9 +774,9 @@ template <int CM>
 struct SqlRec {
   uint64_t hdr, sq;
   int64_t c[CM];
-  __device__ uint32_t key() const { return (uint32_t)hdr; }
-  __device__ uint32_t krel(uint32_t kbase) const { return kbase + (uint32_t)((hdr >> 32) & 0xFFFFull); }
-  __device__ bool present(int k) const { return (hdr >> (56 + k)) & 1ull; }
+  __device__ uint32_t key() const { return part_key(hdr); }
+  __device__ uint32_t krel(uint32_t kbase) const { return part_krel(true, hdr, kbase); }
+  __device__ bool present(int k) const { return part_present(true, hdr, 0, k); }
   __device__ int64_t col(int k) const {
     int64_t v = 0;
 #pragma unroll
@@ -815,8 +784,8 @@ struct SqlRec {
       if (q == k) v = c[q];
     return v;
   }
-  __device__ int64_t seq1() const { return (int64_t)(sq & kSeqMask); }
-  __device__ bool dec(int k) const { return (sq >> (56 + k)) & 1ull; }
+  __device__ int64_t seq1() const { return seqw_seq1(sq); }
+  __device__ bool dec(int k) const { return seqw_dec(sq, k); }
 };
 
 // whether phase 2 has anything to do for this record (from its header and

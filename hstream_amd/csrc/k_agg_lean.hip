@@ -54,15 +54,6 @@ __device__ inline uint32_t lean_sort_bin(const TwTable &t, const PartParams &pp,
   return span > 10 ? (uint32_t)(local >> (span - 10)) : (uint32_t)local;
 }
 
-// value of slot s for one packed record (COUNT(col) slots of batches without
-// validity arrays are filled from COUNT(*) at write-out)
-template <int NS, uint64_t SIG, int W>
-__device__ inline void lean_elems(const PRec<W, true> &r, int64_t (&v)[NS]) {
-  const ProgSig<SIG> prog;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) v[s] = prec_elem(prog, s, r);
-}
-
 // chunk of this workgroup: records [r0, r1) of bucket b; false past the chunks
 __device__ inline bool lean_chunk(const PartParams &pp, const PartBuffers &pb, uint32_t &b, uint64_t &r0,
                                   uint64_t &r1, bool &exclusive) {
@@ -174,8 +165,9 @@ __global__ __launch_bounds__(NT) void k_agg_lean(PartParams pp, TwTable t, PartB
         lds_apply<NS, E>(prog, &lagg[e], r, skip);
       } else {
         // no room: this record is a partial of its own
+        // (COUNT(col) of a batch without validity arrays = COUNT(*))
         int64_t v[NS];
-        lean_elems<NS, SIG, W>(r, v);
+        rec_elems<NS>(prog, r, v);
         if (skip) {
 #pragma unroll
           for (int s = 0; s < NS; ++s)

@@ -14,7 +14,7 @@
 //                sequence words) in HBM-home order;
 //   k_sql_apply  one workgroup per aggregation workgroup: its partials into
 //                the HBM (key, window) table with the full slot algebra
-//                (hsg_dev.h combine_row: tie words, the LAST pair, form
+//                (hsg_slots.h combine_row: tie words, the LAST pair, form
 //                slots) and the per-batch changelog rows written directly.
 //
 // The order-dependent slots need more than one LDS atomic per slot. The

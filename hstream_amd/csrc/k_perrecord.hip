@@ -119,7 +119,7 @@ __device__ inline void pair_elem(const Program &prog, const Batch &b, const PrBu
                                  uint64_t rec_base, uint32_t pidx, int64_t (&e)[MS]) {
   const uint32_t rec = pb.prec[pidx];
   const uint64_t seq1 = (seq ? (uint64_t)seq[rec] : rec_base + rec) + 1;
-  elem_row<MS>(prog, e, b, rec, seq1);
+  rec_elems<MS>(prog, BatchRec{b, rec, seq1}, e);
 }
 
 // (hf, v) <- (hf_u, v_u) (+) (hf, v): segmented combine, u earlier

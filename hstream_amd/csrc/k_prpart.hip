@@ -58,56 +58,15 @@ struct PrRecView {
   const uint64_t *w;
   bool pk;
   int C;
-  __device__ uint32_t key() const { return (uint32_t)w[0]; }
-  __device__ uint32_t krel(uint32_t kbase) const {
-    return pk ? kbase + (uint32_t)((w[0] >> 32) & 0xFFFFull) : (uint32_t)(w[0] >> 32);
-  }
-  __device__ uint32_t nwin() const { return pk ? (uint32_t)((w[0] >> 48) & 0xFFull) : (uint32_t)w[1]; }
-  __device__ bool present(int c) const { return pk ? (w[0] >> (56 + c)) & 1ull : (w[1] >> (32 + c)) & 1ull; }
+  __device__ uint32_t key() const { return part_key(w[0]); }
+  __device__ uint32_t krel(uint32_t kbase) const { return part_krel(pk, w[0], kbase); }
+  // (word 1 of a packed record is not its own when it has no column: not read)
+  __device__ uint32_t nwin() const { return part_nwin(pk, w[0], w[pk ? 0 : 1]); }
+  __device__ bool present(int c) const { return part_present(pk, w[0], w[pk ? 0 : 1], c); }
   __device__ int64_t col(int c) const { return (int64_t)w[(pk ? 1 : 2) + c]; }
-  // the sequence word (hsg_dev.h seq_word): seq + 1, decimal-literal bits
-  __device__ int64_t seq1() const { return (int64_t)(w[(pk ? 1 : 2) + C] & kSeqMask); }
-  __device__ bool dec(int c) const { return (w[(pk ? 1 : 2) + C] >> (56 + c)) & 1ull; }
+  __device__ int64_t seq1() const { return seqw_seq1(w[(pk ? 1 : 2) + C]); }
+  __device__ bool dec(int c) const { return seqw_dec(w[(pk ? 1 : 2) + C], c); }
 };
-
-// contribution of the record to every slot (identity when the field is absent)
-template <int MS, class RV>
-__device__ inline void pr_elems(const Program &prog, const RV &r, int64_t (&e)[MS]) {
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    e[s] = 0;
-    if (s >= prog.n_slots) continue;
-    const int op = prog.slot_op[s], c = prog.slot_col[s];
-    if (op == S_CNT_ALL) {
-      e[s] = 1;
-      continue;
-    }
-    const bool pr = r.present(c);
-    if (op == S_LAST_VAL) {
-      e[s] = pr ? r.col(c) : 0;
-      continue;
-    }
-    if (!pr) {
-      e[s] = slot_identity_dev(op);
-      continue;
-    }
-    switch (op) {
-      case S_CNT: e[s] = 1; break;
-      case S_SUM_I:
-      case S_SUM_F:
-      case S_MIN_I:
-      case S_MAX_I: e[s] = r.col(c); break;
-      case S_MIN_F:
-      case S_MAX_F: e[s] = (int64_t)f64_ord(__builtin_bit_cast(double, r.col(c))); break;
-      case S_LAST_SEQ: e[s] = r.seq1(); break;
-      case S_CNT_DEC: e[s] = r.dec(c) ? 1 : 0; break;
-      case S_TIE_MIN:
-      case S_TIE_MAX:
-      case S_LAST_FORM: e[s] = (int64_t)(((uint64_t)r.seq1() << 1) | (r.dec(c) ? 0u : 1u)); break;
-      default: break;
-    }
-  }
-}
 
 // (hf, v) <- (hf_u, v_u) (+) (hf, v), u earlier: segmented combine
 template <int MS>
@@ -389,7 +348,7 @@ __global__ __launch_bounds__(kPrNT) void k_pr_local(Program prog, PartParams pp,
       hd[k] = q == 0 || (sorted[q - 1] >> 16) != (v >> 16);
       const uint32_t rr = prp[v & 0xFFFFu] >> 8;
       const PrRecView rv{pb.rec + (r0 + rr) * (uint64_t)W, pk, C};
-      pr_elems<MS>(prog, rv, e[k]);
+      rec_elems<MS>(prog, rv, e[k]);
     } else {
       identity_row<MS>(prog, e[k]);
     }
@@ -879,8 +838,10 @@ __global__ __launch_bounds__(kPrEmitThreads) void k_pr_emit(Batch bt, Program pr
 constexpr int kPbNT = 256;
 constexpr int kPbNW = kPbNT / 64;
 
-// Slot-program helpers over a program view (ProgRT, or ProgSig<SIG> with the
-// slot ops baked in: the common aggregate sets get straight-line combines)
+// combine_v / identity_v / elems_v: local forms of combine_row, identity_row
+// and rec_elems (hsg_slots.h) for k_pr_bucket and k_pr_keys, as are PrRecRegs'
+// own decodes: over the shared routines k_pr_keys<8> loses occupancy (3 -> 2)
+// and the 16-slot variants gain scratch.
 template <int MS, class PV>
 __device__ inline void combine_v(const PV &pv, int64_t (&a)[MS], const int64_t (&e)[MS]) {
   if constexpr (std::is_same<PV, ProgRT>::value) {
@@ -1012,7 +973,6 @@ struct PrRecRegs {
     return (int64_t)(k == 0 ? r0 : k == 1 ? r1 : k == 2 ? r2 : r3);
   }
   __device__ int64_t col(int c) const { return word((pk ? 1 : 2) + c); }
-  // the sequence word (hsg_dev.h seq_word): seq + 1, decimal-literal bits
   __device__ int64_t seq1() const { return (int64_t)((uint64_t)word((pk ? 1 : 2) + C) & kSeqMask); }
   __device__ bool dec(int c) const { return ((uint64_t)word((pk ? 1 : 2) + C) >> (56 + c)) & 1ull; }
 };

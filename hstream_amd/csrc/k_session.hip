@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void k_ss_process(Batch b, SessParams p, SessT
       // aggF initialValue r, then mergeF acc cur over the overlapped sessions
       int64_t acc[MS], ev[MS];
       identity_row<MS>(prog, acc);
-      elem_row<MS>(prog, ev, b, i, seq1);
+      rec_elems<MS>(prog, BatchRec{b, i, seq1}, ev);
       combine_row<MS>(prog, acc, ev);
       int64_t s0 = ts, e0 = ts;
       for (uint64_t k = i0; k < i1; ++k) {
@@ -658,33 +658,9 @@ void launch_ss_pscatter(hipStream_t s, const Batch &b, int np_log2, int bshift, 
 // ---------------------------------------------------------------------------
 constexpr int kMgTail = 2;  // resident sessions a key may rewrite in place (held in registers)
 
-// contribution of one partitioned record to the slots (identity when absent)
-template <int MS, class PV>
-__device__ __attribute__((always_inline)) inline void ss_rec_elem(const PV &prog, const uint64_t *rec, int64_t (&e)[MS]) {
-  const uint64_t vb = rec[0] >> 32;
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    e[s] = 0;
-    if (s >= prog.n()) continue;
-    const int op = prog.op(s), c = prog.col(s);
-    if (op == S_CNT_ALL) {
-      e[s] = 1;
-      continue;
-    }
-    if (!((vb >> c) & 1ull)) {
-      e[s] = slot_identity_dev(op);
-      continue;
-    }
-    const int64_t v = (int64_t)rec[2 + c];
-    switch (op) {
-      case S_CNT: e[s] = 1; break;
-      case S_MIN_F:
-      case S_MAX_F: e[s] = (int64_t)f64_ord(__builtin_bit_cast(double, v)); break;
-      default: e[s] = v; break;
-    }
-  }
-}
-
+// a <- a (+) e on the merge path: combine_row for its programs, which have no
+// LAST pair and no tie words (session.cpp ss_merge), without combine_row's
+// tests for them in the sweep's inner loop.
 template <int MS, class PV>
 __device__ __attribute__((always_inline)) inline void acc_row(const PV &prog, int64_t (&a)[MS], const int64_t (&e)[MS]) {
 #pragma unroll
@@ -1012,6 +988,8 @@ __device__ inline int64_t ts_of(uint64_t img) { return (int64_t)(img ^ 0x8000000
 
 // contribution of one record (word 0 and columns in `v`, as in the LDS copy:
 // v[0] = key | valid bits << 32, v[1 + c] = column c)
+// A local form of rec_elems (hsg_slots.h) with the f64 MIN / MAX clamp of a
+// point session: over rec_elems and a record view k_ss_apply<8> gains scratch.
 template <int MS, class PV>
 __device__ __attribute__((always_inline)) inline void ss_vw_elem(const PV &prog, const uint64_t *v, int64_t (&e)[MS]) {
   const uint64_t vb = v[0] >> 32;
@@ -1442,6 +1420,7 @@ template <int MS, int W, uint64_t SIG>
 __global__ __launch_bounds__(kApNT) void k_ss_apply(SessParams p, SessTable t, Program prog, SessPart sp,
                                                     OutCols out, uint64_t out_base, DevScalars *sc) {
   const ProgView<SIG> pv(prog);  // the common aggregate sets: slot ops baked in
+  static_assert(!ProgSig<SIG>::has_last_or_forms(), "the merge path's records carry no sequence or literal form");
   __shared__ uint64_t ws[kApNT / 64];
   __shared__ uint64_t we[kApNT / 64];
   __shared__ uint64_t sbase, sobase, srbase;
@@ -1657,11 +1636,10 @@ struct RunsLds {
   __device__ int64_t end(uint32_t r) const { return L->re[r]; }
   template <int MS, class PV>
   __device__ void aggs(const PV &prog, uint32_t r, int64_t (&a)[MS]) const {
-#pragma unroll
-    for (int s = 0; s < MS; ++s) a[s] = s < prog.n() ? slot_identity_dev(prog.op(s)) : 0;
+    identity_row<MS>(prog, a);
     for (uint32_t q = L->rbeg[r]; q < L->rbeg[r + 1]; ++q) {
       int64_t e[MS];
-      ss_rec_elem<MS>(prog, recs + (uint64_t)L->idx[q] * W, e);
+      rec_elems<MS>(prog, SessRec<>(recs + (uint64_t)L->idx[q] * W), e);
       acc_row<MS>(prog, a, e);
     }
   }
@@ -2153,44 +2131,6 @@ void launch_br_subhist(hipStream_t s, const SessTable &t, int np_log2, int bshif
   }
 }
 
-// contribution of a bucket-replay record (present bits 32..39, literal-form
-// bits 40..47 of word 0) to every slot, LAST / form slots included
-template <int MS>
-__device__ inline void br_elem(const Program &prog, const uint64_t *rec, uint64_t seq1, int64_t (&e)[MS]) {
-  const uint64_t vb = rec[0] >> 32;
-#pragma unroll
-  for (int s = 0; s < MS; ++s) {
-    e[s] = 0;
-    if (s >= prog.n_slots) continue;
-    const int op = prog.slot_op[s], c = prog.slot_col[s];
-    if (op == S_CNT_ALL) {
-      e[s] = 1;
-      continue;
-    }
-    const bool present = ((vb >> c) & 1ull) != 0, dec = ((vb >> (8 + c)) & 1ull) != 0;
-    const int64_t x = (int64_t)rec[2 + c];
-    if (op == S_LAST_VAL) {
-      e[s] = present ? x : 0;
-      continue;
-    }
-    if (!present) {
-      e[s] = slot_identity_dev(op);
-      continue;
-    }
-    switch (op) {
-      case S_CNT: e[s] = 1; break;
-      case S_MIN_F:
-      case S_MAX_F: e[s] = (int64_t)f64_ord(__builtin_bit_cast(double, x)); break;
-      case S_LAST_SEQ: e[s] = (int64_t)seq1; break;
-      case S_CNT_DEC: e[s] = dec ? 1 : 0; break;
-      case S_TIE_MIN:
-      case S_TIE_MAX:
-      case S_LAST_FORM: e[s] = (int64_t)((seq1 << 1) | (dec ? 0u : 1u)); break;
-      default: e[s] = x; break;
-    }
-  }
-}
-
 // LDS of k_br_replay. CW: words of each record cached here (its word 0, ts
 // and columns, for records of <= 5 words), so the replay reads no record
 // from HBM; wider records are read from the bucket (L2).
@@ -2420,7 +2360,7 @@ __global__ __launch_bounds__(kBrNT) __attribute__((amdgpu_waves_per_eu(HSG_BR_WP
         // aggF initialValue r, then mergeF acc cur over the overlapped sessions
         int64_t acc[MS], ev[MS];
         identity_row<MS>(prog, acc);
-        br_elem<MS>(prog, rec, seq1, ev);
+        rec_elems<MS>(prog, SessRec<40>(rec, seq1), ev);
         combine_row<MS>(prog, acc, ev);
         int64_t ss = ts, se = ts;
         if (lv && ts >= ls) {

@@ -32,9 +32,8 @@ namespace hsg {
 // Hopping ops on the partition path: k_seg_apply checks its deferred window
 // updates against the table's room and holds back past it (op_device.cpp
 // resume_deferred), so the table follows the groups the batches make.
-static bool has_last(const Program &prog);
 static bool defer_room_checked(const OpDevice &d, const hsg_op_config &cfg, const Program &prog) {
-  return d.use_part && cfg.window_kind == HSG_HOPPING && cfg.emit_mode != HSG_EMIT_PER_RECORD && !has_last(prog);
+  return d.use_part && cfg.window_kind == HSG_HOPPING && cfg.emit_mode != HSG_EMIT_PER_RECORD && !prog_needs_seq(prog);
 }
 
 static uint64_t next_pow2(uint64_t v) {
@@ -73,9 +72,6 @@ static uint64_t ts_stage_count(uint64_t cap) {
   const uint64_t full = cap * sizeof(T);
   return ((full > ts16 ? full : ts16) + sizeof(T) - 1) / sizeof(T);
 }
-
-// LAST, or literal-form slots: the records' global sequence numbers are needed
-static bool has_last(const Program &prog) { return prog_needs_seq(prog); }
 
 static int alloc_out(OutCols &o, uint64_t cap, int n_aggs, std::string &err, bool forms = false) {
   if (forms) DTRY(dalloc(&o.form, cap));
@@ -808,7 +804,7 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
   // batch that is not one (late records, a wide layout) runs again on the
   // record kernels (k_window.hip k_tw_agg and its LAST / tie resolution pass)
   const bool sql = d.sql_lean;
-  const bool opt = d.use_part && !rec_wm && (!has_last(prog) || sql) && cfg.grace_ms >= 0 &&
+  const bool opt = d.use_part && !rec_wm && (!prog_needs_seq(prog) || sql) && cfg.grace_ms >= 0 &&
                    cfg.window_kind != HSG_SESSION;
   const bool need_epoch = !d.h_sc->epoch_set;
   // Table room (see table_bound_hint): the partition path's claiming kernels
@@ -891,7 +887,7 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
       wait_table_reset(d);
       launch_tw_agg(d.stream, kb, p, d.tw, prog, d.tile_prefix, rec_wm, seq, d.sc, false);
     }
-    if (has_last(prog) && !(sql && part_now))
+    if (prog_needs_seq(prog) && !(sql && part_now))
       launch_tw_agg(d.stream, kb, p, d.tw, prog, d.tile_prefix, rec_wm, seq, d.sc, true);
     if (cfg.emit_mode == HSG_EMIT_PER_BATCH) {
       if (part_now) {
@@ -1067,7 +1063,7 @@ static uint64_t table_bound_hint(const OpDevice &d, const hsg_op_config &cfg, co
   // in-kernel updates have no check of their own, gets the worst case
   if (defer_room_checked(d, cfg, prog)) return d.defer_pred ? d.defer_pred : UINT64_MAX;
   if (d.sql_lean) return cfg.grace_ms >= 0 ? d.lean_pred : UINT64_MAX;  // k_sql_apply checks its partials
-  if (!d.use_part || has_last(prog) || cfg.emit_mode == HSG_EMIT_PER_RECORD || cfg.grace_ms < 0 ||
+  if (!d.use_part || prog_needs_seq(prog) || cfg.emit_mode == HSG_EMIT_PER_RECORD || cfg.grace_ms < 0 ||
       cfg.window_kind == HSG_SESSION || cfg.n_cols > 8 || d.wpr >= 256)
     return UINT64_MAX;
   PartParams q;

@@ -37,9 +37,6 @@ static int log2u(uint64_t v) {
   return l;
 }
 
-// LAST, or literal-form slots: the records' global sequence numbers are needed
-static bool has_last(const Program &prog) { return prog_needs_seq(prog); }
-
 static int alloc_keys(SessTable &t, uint64_t kcap, std::string &err) {
   DTRY(hipMalloc((void **)&t.kt, kcap * sizeof(SessKey)));
   t.kmask = kcap - 1;
@@ -154,7 +151,7 @@ int session_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &pr
   DTRY(hipHostMalloc((void **)&d.h_regions, kArenaRegions * kRegionStride * sizeof(uint64_t), hipHostMallocDefault));
   // HSG_SS_REPLAY_ALL=1: per-batch / state-only ops on the bucket replay too (A/B)
   static const bool replay_all = getenv("HSG_SS_REPLAY_ALL") != nullptr;
-  d.ss_merge = cfg.emit_mode != HSG_EMIT_PER_RECORD && !has_last(prog) && !prog_has_forms(prog) &&
+  d.ss_merge = cfg.emit_mode != HSG_EMIT_PER_RECORD && !prog_needs_seq(prog) && !prog_has_forms(prog) &&
                prog.n_slots <= 8 && !replay_all;
   rc = part_device_init(d, cfg, prog, err);
   if (rc != HSG_OK) return rc;

@@ -90,10 +90,6 @@ int perrecord_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &
 // Per-record changelog on the partitioned pipeline (k_prpart.hip): ops with
 // <= 8 state slots and < 256 windows per record. Others: the sort path below.
 // ---------------------------------------------------------------------------
-// LAST, or literal-form slots: the records' sequence words (global seq +
-// literal bits) ride in the partitioned records
-static bool has_last_slot(const Program &prog) { return prog_part_seq(prog); }
-
 // the per-record kernels fold with the full slot algebra (combine_row: the
 // LAST pair, tie words, literal-form slots), up to 16 slots
 bool perrecord_part_eligible(const Program &prog, uint64_t wpr) { return prog.n_slots <= 16 && wpr < 256; }
@@ -156,7 +152,7 @@ static int push_time_perrecord_part(OpDevice &d, const hsg_op_config &cfg, const
   // batch with late records runs again with per-record stream time
   const bool opt = !rec_wm && cfg.grace_ms >= 0;
   const bool need_epoch = !d.h_sc->epoch_set;
-  const bool last = has_last_slot(prog);
+  const bool last = prog_part_seq(prog);
   auto run = [&](bool optimistic) -> int {
     int rc = clear_batch_scalars(d, err);
     if (rc != HSG_OK) return rc;

@@ -1,8 +1,11 @@
 """GPU: every aggregation path on full-width int64 and extreme f64 values.
 
 The per-slot aggregate logic (S_SUM_I, S_MIN_F, f64_ord, the tie words, LAST)
-is written out once per kernel family; the rest of the suite varies windows,
-emit modes, skew and transports over values near 1e0 .. 1e9. Here one driver
+is written once (csrc/hsg_slots.h) and instantiated per kernel family, each
+over its own record layout, except that k_part_agg, k_pr_bucket / k_pr_keys,
+k_agg_sql and k_ss_apply keep local forms of it (their register budgets);
+the rest of the suite varies windows, emit modes, skew and transports over
+values near 1e0 .. 1e9. Here one driver
 pushes tests/valgen.py's columns -- int64 with a live high word, the int64
 identities as real values, sums that cross +-2^63 in any order but arrival
 order, doubles at the ends of the format, subnormal sums -- through

@@ -24,6 +24,7 @@ STATUS_NAMES = {
 }
 
 HSG_KEY_NONE = 0xFFFFFFFF
+HSG_VIEW_MAX_KEYS = 1024  # hsg_view_get
 HSG_TRANSPORT_RCCL = 0
 HSG_TRANSPORT_HOST = 1
 HSG_COMM_ID_BYTES = 128
@@ -263,6 +264,7 @@ EXPORTED_SYMBOLS = [
     "hsg_op_set_changelog",
     "hsg_state_rows",
     "hsg_dump_state",
+    "hsg_view_get",
     "hsg_op_stats",
     "hsg_testing_set_knob",
 ]
@@ -279,6 +281,7 @@ INGEST_SYMBOLS = [
     "hsg_keydict_destroy",
     "hsg_keydict_size",
     "hsg_keydict_encode",
+    "hsg_keydict_find",
     "hsg_keydict_text",
     "hsg_keydict_spelling_text",
     "hsg_decoder_create",

@@ -7,6 +7,7 @@
 // Every entry point catches everything: no C++ exception crosses the ABI.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -866,6 +867,28 @@ extern "C" int hsg_dump_state(hsg_op *op, hsg_rows *out, uint64_t *n_out) {
     rc = op_dump(op->dev, op->cfg, op->prog, out, &n, op->err);
     *n_out = n;
     return rc;
+  } catch (...) {
+    return HSG_E_DEVICE;
+  }
+}
+
+extern "C" int hsg_view_get(hsg_op *op, const uint32_t *key_ids, uint32_t n_keys, hsg_rows *out, uint64_t *n_out) {
+  try {
+    if (!op || !n_out) return HSG_E_INVALID;
+    wait_idle(op);
+    int rc = check_rows(op, out);
+    if (rc != HSG_OK) return rc;
+    *n_out = 0;
+    if (n_keys > HSG_VIEW_MAX_KEYS) return fail(op->err, HSG_E_INVALID, "view_get: more than HSG_VIEW_MAX_KEYS keys");
+    if (n_keys && !key_ids) return fail(op->err, HSG_E_INVALID, "view_get: null key_ids");
+    if (n_keys == 0) return HSG_OK;
+    // duplicates count once; HSG_KEY_NONE names no group
+    std::vector<uint32_t> keys(key_ids, key_ids + n_keys);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    if (!keys.empty() && keys.back() == HSG_KEY_NONE) keys.pop_back();
+    HIP_TRY(op, hipSetDevice(op->eng->device));
+    return op_view_get(op->dev, op->cfg, op->prog, keys.data(), (uint32_t)keys.size(), out, n_out, op->err);
   } catch (...) {
     return HSG_E_DEVICE;
   }

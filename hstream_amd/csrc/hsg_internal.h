@@ -240,6 +240,13 @@ __device__ __host__ inline uint64_t key_hash(uint32_t key) {
   const uint32_t h = fmix32(key * 0x9E3779B1u + 0x632BE59Bu);
   return ((uint64_t)h << 32) | (uint32_t)((h * 0x27D4EB2Fu) ^ key);
 }
+// First slot of the table region that holds every group of g's key (regions:
+// hsg_tw.h). rbits == 0: the region is the table.
+__device__ __host__ inline uint64_t tw_region_base(const TwTable &t, uint64_t g) {
+  if (!t.rbits) return 0;
+  const uint64_t r = (key_hash((uint32_t)(g >> 32)) << t.bshift) >> (64 - t.rbits);
+  return r * (t.rmask + 1);
+}
 __device__ __host__ inline int log2_exact(uint32_t g) {  // -1 unless g is a power of two
   if (g == 0 || (g & (g - 1))) return -1;
   int l = 0;

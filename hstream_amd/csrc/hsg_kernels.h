@@ -37,6 +37,43 @@ int push_session(OpDevice &d, const hsg_op_config &cfg, const Program &prog, con
 void launch_session_dump(OpDevice &d, const hsg_op_config &cfg, const Program &prog, OutCols out, uint64_t cap,
                          uint64_t *counter);
 
+// keyed view reads (hsg_view_get: op_device.cpp op_view_get / k_view.hip).
+// Every launcher takes the request's keys sorted ascending, distinct, without
+// HSG_KEY_NONE, in device memory (nk <= HSG_VIEW_MAX_KEYS).
+//
+// Time windows: the slots scanned are the distinct key-hash regions of the
+// requested keys (tw_region_base) and the overflow rows, cut into chunks of
+// kEmitChunk slots, one workgroup each: chunks [0, n_regions * cpr) cover the
+// regions in the order of `region`, the rest the overflow rows.
+struct ViewScan {
+  const uint64_t *region;  // device: first slot of each distinct region, ascending
+  uint32_t n_regions;
+  uint32_t cpr;            // chunks per region
+  uint64_t rslots;         // slots per region
+  uint64_t ovf_base;       // first overflow row (0 slots: none scanned)
+  uint64_t ovf_slots;
+  uint64_t chunks() const { return (uint64_t)n_regions * cpr + (ovf_slots + kEmitChunk - 1) / kEmitChunk; }
+};
+// chunk counts -> es.cnt, their exclusive scan -> es.off, the total -> *total (device)
+void launch_view_tw_count(hipStream_t s, const TwTable &t, const ViewScan &v, const uint32_t *keys, uint32_t nk,
+                          const EmitScratch &es, uint64_t *total);
+// the counted rows, rendered, at out[es.off[chunk] ...] in scan order
+void launch_view_tw_rows(hipStream_t s, const TwTable &t, const ViewScan &v, const uint32_t *keys, uint32_t nk,
+                         const Program &prog, const TwParams &p, const EmitScratch &es, OutCols out, uint64_t out_cap,
+                         DevScalars *sc);
+// Unwindowed ops and sessions: one lookup per key (tw_find / ss_find) leaves
+// the key's table slot (-1: absent) and its row count; one workgroup scans the
+// counts into row offsets (off[nk] = the total); the rows come out in key order.
+void launch_view_kv_find(hipStream_t s, const TwTable &t, const uint32_t *keys, uint32_t nk, int64_t *slot,
+                         uint32_t *cnt);
+void launch_view_ss_find(hipStream_t s, const SessTable &t, const uint32_t *keys, uint32_t nk, int64_t *slot,
+                         uint32_t *cnt);
+void launch_view_scan(hipStream_t s, const uint32_t *cnt, uint32_t nk, uint64_t *off);
+void launch_view_kv_rows(hipStream_t s, const TwTable &t, const Program &prog, const uint32_t *keys, uint32_t nk,
+                         const int64_t *slot, const uint64_t *off, OutCols out, uint64_t out_cap);
+void launch_view_ss_rows(hipStream_t s, const SessTable &t, const Program &prog, const uint32_t *keys, uint32_t nk,
+                         const int64_t *slot, const uint64_t *off, OutCols out, uint64_t out_cap);
+
 // multi-GPU key exchange (exchange.cpp / k_exchange.hip)
 int exchange_device_init(OpDevice &d, const hsg_op_config &cfg, uint64_t batch_cap, std::string &err);
 void exchange_device_free(OpDevice &d);

@@ -246,5 +246,9 @@ void tw_retention_reset(OpDevice &d);
 void wait_table_reset(OpDevice &d);
 int op_dump(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const hsg_rows *out, uint64_t *n_out,
             std::string &err);
+// hsg_view_get: the state rows of `keys` (sorted ascending, distinct, no
+// HSG_KEY_NONE, nk <= HSG_VIEW_MAX_KEYS; host memory) in the dump's order
+int op_view_get(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const uint32_t *keys, uint32_t nk,
+                const hsg_rows *out, uint64_t *n_out, std::string &err);
 
 }  // namespace hsg

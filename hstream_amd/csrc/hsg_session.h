@@ -32,6 +32,26 @@ namespace hsg {
 
 constexpr uint32_t kSessEmptyKey = 0xFFFFFFFFu;
 
+// session row i of the arena: [start][end][stamp][aggs...]
+__device__ inline uint64_t *ss_row(const SessTable &t, uint64_t i) { return t.rows + i * t.stride; }
+// home slot of a key in the key table: the top key-hash bits below the owner bits
+__device__ inline uint64_t ss_home(const SessTable &t, uint32_t key) {
+  return t.kbits ? (uint64_t)((key_hash(key) << t.hshift) >> (64 - t.kbits)) : 0ull;
+}
+// Find-only probe of the key table (keyed view reads, k_view.hip): the key's
+// slot, or -1 when the key has no entry. Entries are never freed between
+// rehashes, so the first free slot of the probe sequence ends the search.
+__device__ inline int64_t ss_find(const SessTable &t, uint32_t key) {
+  uint64_t s = ss_home(t, key);
+  for (uint64_t probe = 0; probe <= t.kmask; ++probe) {
+    const uint32_t cur = t.kt[s].key;
+    if (cur == key) return (int64_t)s;
+    if (cur == kSessEmptyKey) return -1;
+    s = (s + 1) & t.kmask;
+  }
+  return -1;
+}
+
 // The arena's free rows are split into regions, each with its own bump
 // pointer, so thousands of workgroups reserving lists do not serialise on one
 // atomic; a workgroup allocates from region (block id mod kArenaRegions).

@@ -20,11 +20,8 @@ namespace hsg {
 // stays together and a probe sequence is as short as plain linear probing at
 // the same load. Unwindowed tables (every group is window 0) hash plainly and
 // probe by 1.
-__device__ inline uint64_t tw_region_base(const TwTable &t, uint64_t g) {
-  if (!t.rbits) return 0;
-  const uint64_t r = (key_hash((uint32_t)(g >> 32)) << t.bshift) >> (64 - t.rbits);
-  return r * (t.rmask + 1);
-}
+// (tw_region_base itself is in hsg_internal.h: the host plans keyed view reads
+// with it, op_device.cpp op_view_get)
 __device__ inline uint64_t tw_home_in(const TwTable &t, uint64_t g) {
   if (!t.blocked) return mix64(g) & t.rmask;
   return ((mix64((g >> 3) * 0x9E3779B97F4A7C15ull) << 3) | (g & 7ull)) & t.rmask;

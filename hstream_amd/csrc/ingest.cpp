@@ -885,6 +885,23 @@ extern "C" int hsg_keydict_encode(hsg_keydict *d, const char *json, size_t len, 
   }
 }
 
+extern "C" int hsg_keydict_find(const hsg_keydict *d, const char *json, size_t len, uint32_t *id) {
+  if (!d || !json || !id) return HSG_E_INVALID;
+  try {
+    std::string c;
+    Dec tmp;
+    Cur cur{json, json + len};
+    if (!canon_value(cur, c, tmp)) return HSG_E_INVALID;
+    cur.ws();
+    if (cur.p != cur.e) return HSG_E_INVALID;
+    const int64_t f = d->find(c.data(), c.size(), hash_bytes(c.data(), c.size()), nullptr);
+    *id = f >= 0 ? (uint32_t)f : HSG_KEY_NONE;
+    return HSG_OK;
+  } catch (const std::bad_alloc &) {
+    return HSG_E_OOM;
+  }
+}
+
 extern "C" int hsg_keydict_text(const hsg_keydict *d, uint32_t id, char *buf, size_t cap, size_t *len) {
   if (!d || !len || id >= d->size()) return HSG_E_INVALID;
   const uint64_t a = d->toff[id], b = d->toff[id + 1];

@@ -10,9 +10,8 @@ namespace hsg {
 
 // ---------------------------------------------------------------------------
 // store helpers: key entries, session rows [start][end][stamp][aggs...]
+// (ss_row, ss_home and the find-only probe ss_find: hsg_session.h)
 // ---------------------------------------------------------------------------
-__device__ inline uint64_t *ss_row(const SessTable &t, uint64_t i) { return t.rows + i * t.stride; }
-
 __device__ inline void ss_copy(const SessTable &dt, uint64_t dst, const SessTable &st, uint64_t src) {
   const uint64_t *a = ss_row(st, src);
   uint64_t *b = ss_row(dt, dst);
@@ -81,14 +80,11 @@ void launch_ss_reset(hipStream_t s, const SessTable &t) {
 
 // find key's slot, inserting it if absent; -1 = table full. `inserted` is set
 // when this call claimed the slot (its entry then still holds an empty list).
-// Home slot: the top key-hash bits below the owner bits, the same bits that
-// pick the key's partition bucket (and sub-bucket), so the keys of a bucket
-// occupy one stretch of the table and the merge path, which walks a bucket's
-// keys in hash order, touches neighbouring entries from neighbouring lanes.
-__device__ inline uint64_t ss_home(const SessTable &t, uint32_t key) {
-  return t.kbits ? (uint64_t)((key_hash(key) << t.hshift) >> (64 - t.kbits)) : 0ull;
-}
-
+// Home slot (ss_home): the top key-hash bits below the owner bits, the same
+// bits that pick the key's partition bucket (and sub-bucket), so the keys of a
+// bucket occupy one stretch of the table and the merge path, which walks a
+// bucket's keys in hash order, touches neighbouring entries from neighbouring
+// lanes.
 __device__ inline int64_t ss_find_or_insert(const SessTable &t, uint32_t key, bool &inserted) {
   uint64_t s = ss_home(t, key);
   inserted = false;

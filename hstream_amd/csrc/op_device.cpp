@@ -1322,4 +1322,135 @@ int op_dump(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const hs
   return rc;
 }
 
+// The rows of the given keys (sorted, distinct, no HSG_KEY_NONE), in the
+// dump's order: hsg_view_get. Count pass, the total to the host (nothing is
+// written when the rows do not fit out->capacity: *n_out = the rows needed,
+// HSG_E_CAPACITY), then the emit pass into a buffer of exactly that many rows
+// and the copy into the caller's columns. Reads only: the op's state, pending
+// rows and changelog columns are not touched.
+int op_view_get(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const uint32_t *keys, uint32_t nk,
+                const hsg_rows *out, uint64_t *n_out, std::string &err) {
+  *n_out = 0;
+  wait_table_reset(d);
+  int rc = fetch_scalars(d, err);
+  if (rc != HSG_OK || nk == 0) return rc;
+  const bool sess = cfg.window_kind == HSG_SESSION, unwin = cfg.window_kind == HSG_UNWINDOWED;
+  const bool scan = !sess && !unwin;
+  struct DevMem {
+    void *p = nullptr;
+    ~DevMem() {
+      if (p) hipFree(p);
+    }
+  } work, up;
+  struct OutTmp {
+    OutCols o;
+    OutTmp() { memset(&o, 0, sizeof(o)); }
+    ~OutTmp() { free_out(o); }
+  } tmp;
+
+  // the scan's plan: each distinct region of the keys once, then the overflow rows
+  ViewScan v;
+  memset(&v, 0, sizeof(v));
+  std::vector<uint64_t> reg;
+  if (scan) {
+    for (uint32_t i = 0; i < nk; ++i) reg.push_back(tw_region_base(d.tw, (uint64_t)keys[i] << 32));
+    std::sort(reg.begin(), reg.end());
+    reg.erase(std::unique(reg.begin(), reg.end()), reg.end());
+    v.n_regions = (uint32_t)reg.size();
+    v.rslots = d.tw.rmask + 1;
+    v.cpr = (uint32_t)emit_chunks(v.rslots);
+    v.ovf_base = d.tw.mask + 1;
+    v.ovf_slots = d.tw.omask + 1;
+    if (v.chunks() > 0x7FFFFFFFull) {
+      err = "view_get: the requested keys' regions pass 2^31 chunks";
+      return HSG_E_INVALID;
+    }
+  }
+  // closed windows kept on the host: one pass over their key words
+  std::vector<uint64_t> hits;  // indices of the matching spilled rows
+  if (scan && d.spilled_rows) {
+    const uint32_t st = d.tw.stride;
+    for (uint64_t i = 0; i < d.spilled_rows; ++i)
+      if (std::binary_search(keys, keys + nk, (uint32_t)(d.spill[i * st] >> 32))) hits.push_back(i);
+  }
+
+  // device scratch, one allocation: [off][partial][total] (8 B), [regions | slots] (8 B), [cnt][keys] (4 B)
+  const uint64_t nb = scan ? v.chunks() : nk;
+  const uint64_t n_off = nb + 1, n_part = scan ? scan_partials_needed(nb) + 8 : 0, n_aux = scan ? reg.size() : nk;
+  DTRY(hipMalloc(&work.p, (n_off + n_part + 1 + n_aux) * 8 + (nb + nk) * 4));
+  uint64_t *d_off = (uint64_t *)work.p, *d_part = d_off + n_off, *d_total = d_part + n_part, *d_aux = d_total + 1;
+  uint32_t *d_cnt = (uint32_t *)(d_aux + n_aux), *d_keys = d_cnt + nb;
+  EmitScratch es;
+  es.cnt = d_cnt;
+  es.off = d_off;
+  es.partial = d_part;
+  DTRY(hipMemcpyAsync(d_keys, keys, nk * 4ull, hipMemcpyHostToDevice, d.stream));
+  if (scan) {
+    DTRY(hipMemcpyAsync(d_aux, reg.data(), reg.size() * 8, hipMemcpyHostToDevice, d.stream));
+    v.region = d_aux;
+    launch_view_tw_count(d.stream, d.tw, v, d_keys, nk, es, d_total);
+  } else {
+    if (sess) launch_view_ss_find(d.stream, d.ss, d_keys, nk, (int64_t *)d_aux, d_cnt);
+    else launch_view_kv_find(d.stream, d.tw, d_keys, nk, (int64_t *)d_aux, d_cnt);
+    launch_view_scan(d.stream, d_cnt, nk, d_off);
+    d_total = d_off + nk;
+  }
+  DTRY(hipGetLastError());
+  uint64_t found = 0;
+  DTRY(hipMemcpyAsync(&found, d_total, 8, hipMemcpyDeviceToHost, d.stream));
+  DTRY(hipStreamSynchronize(d.stream));
+  const uint64_t total = found + hits.size();
+  *n_out = total;
+  if (total > out->capacity) {
+    err = "view_get: rows capacity < the keys' rows";
+    return HSG_E_CAPACITY;
+  }
+  if (total == 0) return HSG_OK;
+
+  rc = alloc_out(tmp.o, total, cfg.n_aggs, err, d.forms);
+  if (rc != HSG_OK) return rc;
+  PushArgs a;
+  const TwParams p = make_tw_params(cfg, a);
+  if (scan) {
+    if (found) launch_view_tw_rows(d.stream, d.tw, v, d_keys, nk, prog, p, es, tmp.o, found, d.sc);
+  } else if (sess) {
+    launch_view_ss_rows(d.stream, d.ss, prog, d_keys, nk, (const int64_t *)d_aux, d_off, tmp.o, found);
+  } else {
+    launch_view_kv_rows(d.stream, d.tw, prog, d_keys, nk, (const int64_t *)d_aux, d_off, tmp.o, found);
+  }
+  DTRY(hipGetLastError());
+  std::vector<uint64_t> packed;
+  if (!hits.empty()) {
+    // the matching raw rows go up in one copy and are rendered, as a dense
+    // "table", by the emit kernel tw_dump_spilled uses, behind the resident rows
+    const uint32_t st = d.tw.stride;
+    const uint64_t m = hits.size(), mb = emit_chunks(m);
+    packed.resize(m * st);
+    for (uint64_t i = 0; i < m; ++i) memcpy(&packed[i * st], &d.spill[hits[i] * st], st * 8ull);
+    const uint64_t row_words = m * st, n_sp = scan_partials_needed(mb) + 8;
+    DTRY(hipMalloc(&up.p, (row_words + mb + n_sp + 1) * 8 + mb * 4));
+    uint64_t *u_rows = (uint64_t *)up.p, *u_off = u_rows + row_words, *u_part = u_off + mb, *u_total = u_part + n_sp;
+    EmitScratch ses;
+    ses.off = u_off;
+    ses.partial = u_part;
+    ses.cnt = (uint32_t *)(u_total + 1);
+    DTRY(hipMemcpyAsync(u_rows, packed.data(), row_words * 8, hipMemcpyHostToDevice, d.stream));
+    TwTable st_tab = d.tw;
+    st_tab.rows = u_rows;
+    launch_tw_emit(d.stream, st_tab, m, prog, p, 1, tmp.o, found, total, d.sc, ses, u_total);
+    DTRY(hipGetLastError());
+  }
+  rc = op_copy_rows(d, tmp.o, 0, total, cfg.n_aggs, out, err);  // (synchronises the stream)
+  if (rc != HSG_OK) return rc;
+  // keys ascending and lists sorted by start: unwindowed and session rows are
+  // in the dump's order already; time windows come out in slot order
+  if (scan) {
+    const bool dev_sort = out->mem == HSG_MEM_DEVICE && total >= (1ull << 20) && total < 0xFFFFFFFFull && out->key_id &&
+                          out->win_start && out->win_end;
+    rc = dev_sort ? sort_dump_rows_device(d, cfg, out, total, cfg.n_aggs, err)
+                  : sort_dump_rows(d, out, total, cfg.n_aggs, err);
+  }
+  return rc;
+}
+
 }  // namespace hsg

@@ -7,8 +7,10 @@ Engine raises.
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import abi
-from .columnar import OpHandle, OpSpec, declare_op_functions
+from .columnar import OpHandle, OpSpec, Rows, alloc_rows, declare_op_functions, truncate
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhstream_gpu.so")
 # diagnostics only: HSG_LIB_PATH names another build of the same library
@@ -51,6 +53,8 @@ def load_library(path=LIB_PATH):
     L.hsg_push_batch_async.restype = C.c_int
     L.hsg_op_wait.argtypes = [vp]
     L.hsg_op_wait.restype = C.c_int
+    L.hsg_view_get.argtypes = [vp, vp, C.c_uint32, P(abi.hsg_rows), P(C.c_uint64)]
+    L.hsg_view_get.restype = C.c_int
     L.hsg_testing_set_knob.argtypes = [C.c_int32, C.c_int64]
     L.hsg_testing_set_knob.restype = C.c_int
     declare_op_functions(L, "hsg")
@@ -208,6 +212,24 @@ class GpuOp(OpHandle):
     def wait(self):
         """hsg_op_wait: block until the queued pushes are done; raises the first failure."""
         self._check(self._lib.hsg_op_wait(self._h), "op_wait")
+
+    def view_get(self, key_ids, capacity=None) -> Rows:
+        """hsg_view_get: the state rows of the given key ids (at most
+        HSG_VIEW_MAX_KEYS), as dump_state() returns them and in its order. The
+        rows land in host columns of `capacity` rows (default: 64 per key); when
+        they do not fit, the call is made once more with the count it reported."""
+        keys = np.ascontiguousarray(np.asarray(key_ids, dtype=np.uint32).ravel())
+        cap = int(capacity) if capacity is not None else 64 * max(1, keys.size)
+        for attempt in (0, 1):
+            rows, arrs, keep = alloc_rows(cap, self._f64, self._forms)
+            got = C.c_uint64(0)
+            rc = self._lib.hsg_view_get(self._h, keys.ctypes.data if keys.size else None, keys.size, C.byref(rows),
+                                        C.byref(got))
+            if rc == abi.HSG_E_CAPACITY and attempt == 0:
+                cap = got.value
+                continue
+            self._check(rc, "view_get")
+            return truncate(arrs, got.value)
 
     def stats(self) -> dict:
         s = abi.hsg_stats()

@@ -30,6 +30,8 @@ def _lib():
         L.hsg_keydict_size.restype = C.c_uint64
         L.hsg_keydict_encode.argtypes = [vp, C.c_char_p, C.c_size_t, P(C.c_uint32)]
         L.hsg_keydict_encode.restype = C.c_int
+        L.hsg_keydict_find.argtypes = [vp, C.c_char_p, C.c_size_t, P(C.c_uint32)]
+        L.hsg_keydict_find.restype = C.c_int
         L.hsg_keydict_text.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, P(C.c_size_t)]
         L.hsg_keydict_text.restype = C.c_int
         L.hsg_decoder_create.argtypes = [P(abi.hsg_decoder_config), P(vp)]
@@ -80,6 +82,17 @@ class KeyDict:
 
     def encode(self, value) -> int:
         return self.encode_json(json.dumps(value))
+
+    def find_json(self, text) -> int:
+        """hsg_keydict_find: the id of a JSON text's value, or HSG_KEY_NONE when
+        the key was never encoded; the dictionary is left as it is."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        out = C.c_uint32()
+        _check(self._L.hsg_keydict_find(self._h, b, len(b), C.byref(out)), "hsg_keydict_find")
+        return int(out.value)
+
+    def find(self, value) -> int:
+        return self.find_json(json.dumps(value))
 
     def text(self, i: int) -> str:
         n = C.c_size_t()

@@ -140,6 +140,10 @@ class KeyDict:
             self._keys.append(key)
         return i
 
+    def find(self, key) -> int:
+        """The key's id without inserting it (reads): HSG_KEY_NONE when absent."""
+        return self._ids.get(_canon(key), abi.HSG_KEY_NONE)
+
     def decode(self, i: int):
         return self._keys[int(i)]
 
@@ -382,8 +386,48 @@ class Table:
         """ksDump / ssDump (views): every live group."""
         return self._rows(self.op.dump_state())
 
+    def get(self, key):
+        """The rows of one key (ksGet / findSessions), read from HBM by key
+        (hsg_view_get): [] for a key the dictionary has never seen, which is
+        looked up without being inserted."""
+        kid = self.mat.keys.find(key)
+        if kid == abi.HSG_KEY_NONE:
+            return []
+        return self._rows(self.op.view_get([kid]))
+
+    def select_view(self, key):
+        """SELECT ... FROM view WHERE key = x (SelectViewPlan, Handler.hs:277-323)."""
+        return select_view_result(self.get(key), self.windowed, self.spec.window_kind == abi.HSG_SESSION,
+                                  self.spec.size_ms)
+
     def close(self):
         self.op.close()
+
+
+def select_view_result(rows, windowed: bool, session: bool, size_ms: int, names: Optional[Sequence[str]] = None):
+    """The answer of SELECT ... FROM view WHERE key = x for one key's rows, as
+    SelectViewPlan shapes it (hstream/src/HStream/Server/Handler.hs:287-323):
+
+      fixed windows   {"winStart = S ,winEnd = E": values} with E = S + size_ms
+                      (:299-312; no row: the empty object)
+      sessions        {"winStart = S": values} in start order (:315-323)
+      no window       the key's values, or None (ksGet, :313)
+
+    `rows`: Table.get(key)'s pairs, or columnar Rows of one key, whose values
+    are then named by `names` (default "0", "1", ...). Pure: no GPU."""
+    if isinstance(rows, Rows):
+        nm = list(names) if names is not None else [str(j) for j in range(len(rows.aggs))]
+        starts = [int(s) for s in rows.win_start]
+        vals = [{nm[j]: a[i].item() for j, a in enumerate(rows.aggs)} for i in range(len(rows))]
+    else:
+        starts = [k.twkWindow.tWindowStart if isinstance(k, TimeWindowKey) else 0 for k, _ in rows]
+        vals = [v for _, v in rows]
+    if not windowed:
+        return vals[0] if vals else None
+    order = sorted(range(len(starts)), key=starts.__getitem__)
+    if session:
+        return {f"winStart = {starts[i]}": vals[i] for i in order}
+    return {f"winStart = {starts[i]} ,winEnd = {starts[i] + int(size_ms)}": vals[i] for i in order}
 
 
 def runTask(poll, table: Table, max_polls=None, sink=None):

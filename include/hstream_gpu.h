@@ -27,6 +27,10 @@
  *   hsg_dump_state
  *       ksDump / ssDump (Store.hs:59,81 and :143,238-241) used by views
  *       (hstream/src/HStream/Server/Handler.hs:274-321).
+ *   hsg_view_get
+ *       ksGet / findSessions / ssGet (Store.hs:59,243-272) and with them the one
+ *       read of a view, SELECT ... FROM view WHERE key = x (SelectViewPlan,
+ *       hstream/src/HStream/Server/Handler.hs:277-323), by key instead of from a dump.
  *   hsg_agg kinds
  *       the SQL aggregate components of hstream-sql/src/HStream/SQL/Codegen.hs:399-469
  *       (COUNT(*), COUNT(col), SUM, MIN, MAX, non-aggregate passthrough = HSG_LAST)
@@ -388,6 +392,34 @@ int  hsg_op_set_changelog(hsg_op *op, const hsg_rows *dst);
 int  hsg_state_rows(hsg_op *op, uint64_t *n);
 /* Copy every live state row (views). Same capacity rule as hsg_drain. */
 int  hsg_dump_state(hsg_op *op, hsg_rows *out, uint64_t *n_out);
+
+/* Keyed view read: every live state row whose key_id is among key_ids[0,
+ * n_keys) (host memory), the rows hsg_dump_state returns for those keys and
+ * in its order (key_id, win_start, win_end), src_index -1, form filled for
+ * ops with HSG_OPF_LITERAL_FORMS; out may be host or device memory. This is
+ * the reference's one read of a view, SELECT ... FROM view WHERE key = x
+ * (SelectViewPlan, hstream/src/HStream/Server/Handler.hs:277-323): ksGet for
+ * an unwindowed key (at most one row, win_start = win_end = 0), the key's
+ * windows (resident rows, overflow rows and the closed windows kept on the
+ * host, merged), or its sessions in start order. The GPU reads the keys'
+ * key-hash regions of the table (or their entries of the session key table),
+ * not the table: cost follows the keys asked for, not the state's size.
+ *
+ * Duplicates count once; HSG_KEY_NONE, ids never pushed and keys another rank
+ * owns match nothing. n_keys == 0 gives 0 rows; n_keys > HSG_VIEW_MAX_KEYS or
+ * a NULL key_ids with n_keys > 0 gives HSG_E_INVALID. Same capacity rule as
+ * hsg_drain: if the rows do not fit, nothing is written, *n_out is the number
+ * needed (counted before any row is written, so a retry with that capacity
+ * succeeds) and the call returns HSG_E_CAPACITY.
+ *
+ * The call changes nothing: not state, pending changelog rows, registered
+ * changelog columns or hsg_stats. Like every call on an op it first waits for
+ * the op's queued asynchronous pushes, and it is serialised with the op's
+ * other calls by the caller. On a sharded engine it is NOT collective (no
+ * RCCL call, no host-transport step): a rank answers for the keys it owns and
+ * the caller unites the ranks' answers. */
+#define HSG_VIEW_MAX_KEYS 1024
+int  hsg_view_get(hsg_op *op, const uint32_t *key_ids, uint32_t n_keys, hsg_rows *out, uint64_t *n_out);
 
 /* Counters are cumulative since hsg_op_create (hsg_op_reset keeps them);
  * "last batch" fields describe the most recent hsg_push_batch. */

@@ -70,6 +70,12 @@ uint64_t hsg_keydict_size(const hsg_keydict *d);
 /* Id of one JSON value (text), inserting it if new. HSG_E_INVALID for
  * malformed JSON, HSG_E_CAPACITY when 2^32 - 1 keys exist. */
 int  hsg_keydict_encode(hsg_keydict *d, const char *json, size_t len, uint32_t *id);
+/* Id of one JSON value (text) without inserting it, for reads (a view query
+ * for an unknown key must not grow the dictionary): the same Aeson equality
+ * classes as hsg_keydict_encode (1 and 1.0 are one key); *id = HSG_KEY_NONE
+ * and HSG_OK when the key is absent; HSG_E_INVALID for malformed JSON, as
+ * encode. The dictionary is unchanged. */
+int  hsg_keydict_find(const hsg_keydict *d, const char *json, size_t len, uint32_t *id);
 /* The key's JSON text as Aeson's encode prints the value (numbers in
  * Scientific's shortest form: 1.0 -> 1, 0.001 -> 1.0e-3; object members in
  * sorted order). *len = bytes needed; HSG_E_CAPACITY (nothing copied) when

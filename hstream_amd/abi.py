@@ -238,6 +238,8 @@ class hsg_stats(C.Structure):
         ("overflow_rebuilds", C.c_uint64),
         ("where_dropped", C.c_uint64),
         ("where_dropped_total", C.c_uint64),
+        ("having_dropped", C.c_uint64),
+        ("having_dropped_total", C.c_uint64),
     ]
 
     def as_dict(self):
@@ -253,6 +255,9 @@ EXPORTED_SYMBOLS = [
     "hsg_op_create",
     "hsg_where_check",
     "hsg_op_create_where",
+    "hsg_having_check",
+    "hsg_op_create_filtered",
+    "hsg_having_tile_rows",
     "hsg_op_destroy",
     "hsg_op_reset",
     "hsg_last_error",

@@ -33,6 +33,10 @@ class OpSpec:
     # GPU ahead of the aggregate (hsg_op_create_where); None = no filter.
     # col_types then lists the columns only the program reads as well.
     where: Optional[Sequence] = None
+    # HAVING program, the same instruction set over the op's aggregate outputs
+    # (HSG_W_COL j = aggs[j]): the op filters and compacts the changelog rows
+    # each push appends (hsg_op_create_filtered); None = no filter.
+    having: Optional[Sequence] = None
 
     @property
     def literal_forms(self) -> bool:

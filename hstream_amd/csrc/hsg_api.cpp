@@ -172,34 +172,42 @@ int build_program(const hsg_op_config &cfg, const std::vector<int32_t> &col_type
 }  // namespace hsg
 
 // ---------------------------------------------------------------------------
-// WHERE program (include/hstream_gpu.h hsg_where_ins): host type check
+// WHERE / HAVING program (include/hstream_gpu.h hsg_where_ins): host type check
 // ---------------------------------------------------------------------------
+static int validate_config(const hsg_op_config *c, std::string &err);
+
 namespace hsg {
 
-int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, std::string &err) {
-  if (!prog) return fail(err, HSG_E_INVALID, "where: null program");
+// (`what`: "where" over the value columns, "having" over the aggregate outputs)
+static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_t n, const int32_t *col_types,
+                      int32_t n_cols, int32_t max_cols, std::string &err) {
+  if (!prog) return fail(err, HSG_E_INVALID, what + ": null program");
   if (n < 1 || n > HSG_WHERE_MAX_INS)
-    return fail(err, HSG_E_INVALID, "where: program length " + std::to_string(n) + " outside 1.." +
+    return fail(err, HSG_E_INVALID, what + ": program length " + std::to_string(n) + " outside 1.." +
                                         std::to_string(HSG_WHERE_MAX_INS));
-  if (n_cols < 0 || n_cols > kMaxCols || (n_cols > 0 && !col_types))
-    return fail(err, HSG_E_INVALID, "where: bad value columns (max 8)");
+  if (n_cols < 0 || n_cols > max_cols || (n_cols > 0 && !col_types))
+    return fail(err, HSG_E_INVALID, what + ": bad value columns (max " + std::to_string(max_cols) + ")");
   enum { K_VALUE = 0, K_BOOL = 1 };
   int kind[HSG_WHERE_MAX_DEPTH];
+  bool is_f64[HSG_WHERE_MAX_DEPTH];  // a value's static type, as the device carries it (hsg_pred.h)
   int depth = 0;
-  auto at = [&](int pc) { return "where: instruction " + std::to_string(pc) + ": "; };
+  auto at = [&](int pc) { return what + ": instruction " + std::to_string(pc) + ": "; };
   for (int pc = 0; pc < n; ++pc) {
     const hsg_where_ins &in = prog[pc];
     int pops = 0, want = K_VALUE, gives = K_VALUE;
+    bool f64 = false;
     switch (in.op) {
       case HSG_W_COL:
         if (in.arg < 0 || in.arg >= n_cols)
           return fail(err, HSG_E_INVALID, at(pc) + "column " + std::to_string(in.arg) + " out of range");
         if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64)
           return fail(err, HSG_E_INVALID, at(pc) + "bad column type");
+        f64 = col_types[in.arg] == HSG_F64;
         break;
       case HSG_W_I64: break;
       case HSG_W_F64:
         if (!(in.imm.f - in.imm.f == 0.0)) return fail(err, HSG_E_INVALID, at(pc) + "f64 constant is not finite");
+        f64 = true;
         break;
       case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
       case HSG_W_EQ: case HSG_W_NE: case HSG_W_LT: case HSG_W_GT: case HSG_W_LE: case HSG_W_GE:
@@ -215,17 +223,45 @@ int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, 
       if (kind[depth - 1 - k] != want)
         return fail(err, HSG_E_INVALID,
                     at(pc) + (want == K_VALUE ? "a bool used as a value" : "a value used as a bool"));
+    // value value -> value: i64 only when both are
+    for (int k = 0; k < pops && gives == K_VALUE; ++k) f64 |= is_f64[depth - 1 - k];
     depth -= pops;
     if (depth >= HSG_WHERE_MAX_DEPTH)
       return fail(err, HSG_E_INVALID, at(pc) + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
+    is_f64[depth] = gives == K_VALUE && f64;
     kind[depth++] = gives;
   }
   if (depth != 1)
-    return fail(err, HSG_E_INVALID, "where: " + std::to_string(depth) + " results left on the stack, not one");
-  if (kind[0] != K_BOOL) return fail(err, HSG_E_INVALID, "where: the program leaves a value, not a bool");
+    return fail(err, HSG_E_INVALID, what + ": " + std::to_string(depth) + " results left on the stack, not one");
+  if (kind[0] != K_BOOL)
+    return fail(err, HSG_E_INVALID,
+                what + ": the program leaves a value, not a bool (" + (is_f64[0] ? "an f64" : "an i64") + " value)");
   return HSG_OK;
 }
 
+int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, std::string &err) {
+  return prog_check("where", prog, n, col_types, n_cols, kMaxCols, err);
+}
+
+void having_types(const hsg_op_config *cfg, int32_t *types) {
+  for (int j = 0; j < cfg->n_aggs; ++j) {
+    const hsg_agg &g = cfg->aggs[j];
+    if (g.kind == HSG_COUNT_ALL || g.kind == HSG_COUNT) types[j] = HSG_I64;
+    else if (g.kind == HSG_AVG) types[j] = HSG_F64;
+    else types[j] = cfg->col_types[g.column];
+  }
+}
+
+int having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg, std::string &err) {
+  int rc = validate_config(cfg, err);
+  if (rc != HSG_OK) return rc;
+  if (cfg->n_aggs > kMaxAggs) return fail(err, HSG_E_INVALID, "having: more than 16 aggregates");
+  int32_t types[kMaxAggs];
+  having_types(cfg, types);
+  return prog_check("having", prog, n, types, cfg->n_aggs, kMaxAggs, err);
+}
+
+// (also the HAVING program over the aggregate outputs' types: up to kMaxAggs columns)
 void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, WhereProg &out) {
   memset(&out, 0, sizeof(out));
   out.n = n;
@@ -244,6 +280,22 @@ extern "C" int hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32
   try {
     std::string msg;
     const int rc = where_check(prog, n, col_types, n_cols, msg);
+    if (err && err_len) {
+      const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
+      memcpy(err, msg.data(), k);
+      err[k] = 0;
+    }
+    return rc;
+  } catch (...) {
+    return HSG_E_OOM;
+  }
+}
+
+extern "C" int hsg_having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg, char *err,
+                                size_t err_len) {
+  try {
+    std::string msg;
+    const int rc = having_check(prog, n, cfg, msg);
     if (err && err_len) {
       const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
       memcpy(err, msg.data(), k);
@@ -492,9 +544,9 @@ uint64_t hsg_windows_per_record(const hsg_op_config &c) {
   return 1;
 }
 
-// hsg_op_create is the n == 0 case.
-extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
-                                   hsg_op **out) {
+// hsg_op_create is the n == 0, n_having == 0 case.
+extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
+                                      const hsg_where_ins *having, int32_t n_having, hsg_op **out) {
   try {
     if (!eng || !out) return HSG_E_INVALID;
     *out = nullptr;
@@ -503,6 +555,12 @@ extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, co
     if (n != 0) {
       rc = where_check(where, n, cfg->col_types, cfg->n_cols, eng->err);
       if (rc != HSG_OK) return rc;
+    }
+    if (n_having != 0) {
+      rc = having_check(having, n_having, cfg, eng->err);
+      if (rc != HSG_OK) return rc;
+      if (cfg->emit_mode == HSG_EMIT_NONE)
+        return fail(eng->err, HSG_E_INVALID, "having: an op that emits no rows (HSG_EMIT_NONE) has nothing to filter");
     }
     hsg_op *op = new (std::nothrow) hsg_op();
     if (!op) return HSG_E_OOM;
@@ -547,6 +605,13 @@ extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, co
     if (rc != HSG_OK) { delete op; return rc; }
     op->dev.user_cols = cfg->n_cols;
     op->dev.forms = forms;
+    if (n_having != 0) {
+      // the changelog filter (k_having.hip): over the aggregate outputs, as the caller numbers them
+      int32_t otypes[kMaxAggs];
+      having_types(cfg, otypes);
+      where_compile(having, n_having, otypes, cfg->n_aggs, op->dev.having);
+      op->dev.hv.n_aggs = cfg->n_aggs;
+    }
     if (hipSetDevice(eng->device) != hipSuccess) { delete op; return HSG_E_DEVICE; }
     if (eng->comm) {
       // collective over the engine's ranks: every rank creates its sharded ops
@@ -604,8 +669,13 @@ extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, co
   }
 }
 
+extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
+                                   hsg_op **out) {
+  return hsg_op_create_filtered(eng, cfg, where, n, nullptr, 0, out);
+}
+
 extern "C" int hsg_op_create(hsg_engine *eng, const hsg_op_config *cfg, hsg_op **out) {
-  return hsg_op_create_where(eng, cfg, nullptr, 0, out);
+  return hsg_op_create_filtered(eng, cfg, nullptr, 0, nullptr, 0, out);
 }
 
 extern "C" void hsg_op_destroy(hsg_op *op) {
@@ -696,6 +766,13 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
       res.where_dropped = seen - op->dev.where_seen;
       op->dev.where_seen = seen;
     }
+    if (op->dev.having.n && op->dev.hv_ran) {
+      // the changelog filter's kept rows came back with the same fetch
+      // (kHavingWord): the batch appended these, in order, from op->pending
+      const uint64_t kept = op->dev.hv_kept < res.out_rows ? op->dev.hv_kept : res.out_rows;
+      res.having_dropped = res.out_rows - kept;
+      res.out_rows = kept;
+    }
     // state was mutated: account for what happened even on OOM / RANGE
     *inout_watermark = res.wm_out;
     op->pending += res.out_rows;
@@ -722,6 +799,8 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
     op->stats.pending_rows = op->pending;
     op->stats.where_dropped = res.where_dropped;
     op->stats.where_dropped_total += res.where_dropped;
+    op->stats.having_dropped = res.having_dropped;
+    op->stats.having_dropped_total += res.having_dropped;
     op->stats.last_batch_ms = now_ms() - t0;
     op->stats.agg_kernel_ms += res.agg_ms;
     op->stats.agg_kernel_launches += res.agg_launches;

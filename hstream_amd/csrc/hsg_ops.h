@@ -89,6 +89,25 @@ struct OpDevice {
   const hsg_batch *where_staged = nullptr;  // the batch of this push stage_batch already filtered
   Batch where_kb = {};                      // ... and what it resolved to
   uint64_t where_seen = 0;      // the cumulative masked-record count at the last push's end (kWhereWord)
+  // HAVING pushdown (k_having.hip): the program over the op's aggregate
+  // outputs (having.n == 0: none), run by finish_batch over the changelog
+  // segment the batch appended, ahead of the fetch of the scalars. The push
+  // says where the segment is and where its length will be (hv); the fetch
+  // brings back the rows kept (kHavingWord -> hv_ran / hv_kept).
+  WhereProg having = {};
+  struct HavingPass {
+    int32_t n_aggs = 0;
+    uint64_t pending = 0;                 // rows ahead of the batch's segment
+    uint64_t bound = 0;                   // the most rows the batch can append
+    uint64_t host_total = UINT64_MAX;     // the segment's length where the host knows it
+    const uint64_t *dev_total = nullptr;  // else this device word; null: sc->out_rows + sc->scratch[3]
+    const uint64_t *skip = nullptr;       // device word, non-zero = the batch runs again; null: sc->scratch[32]
+    bool hold_emit = false;               // the per-batch emit chain was not launched and may follow the fetch
+  } hv;
+  uint64_t *hv_state = nullptr;  // ticket and tile states of the pass (grow-only; ops with a program only)
+  uint64_t hv_state_words = 0;
+  bool hv_ran = false;           // the last fetch of this push found the pass's word
+  uint64_t hv_kept = 0;
   uint64_t wpr = 1;             // max windows per record
   bool sql_lean = false;        // per-batch LAST / literal-form op on the SQL lean kernels (k_agg_sql.hip)
   bool sql_wide = false;        // ... at 3 - 8 columns or 17 - 24 slots (k_agg_sql_wide.hip; PartParams::sql_wide)
@@ -208,6 +227,7 @@ struct PushResult {
   uint64_t owned = 0;           // records aggregated here after the exchange
   uint64_t global_records = 0;  // records in this batch over all ranks
   uint64_t where_dropped = 0;   // keyed records of this rank's batch the WHERE program masked
+  uint64_t having_dropped = 0;  // changelog rows of this rank's batch the HAVING program removed
   double agg_ms = 0;
   uint64_t agg_launches = 0;
   double exchange_ms = 0;

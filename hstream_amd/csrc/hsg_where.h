@@ -1,6 +1,8 @@
-// WHERE pushdown: the predicate program of include/hstream_gpu.h
-// (hsg_where_ins) as the host checks it (hsg_api.cpp where_check) and as
-// k_where.hip interprets it over a staged batch. Not part of the ABI.
+// WHERE / HAVING pushdown: the predicate program of include/hstream_gpu.h
+// (hsg_where_ins) as the host checks it (hsg_api.cpp where_check /
+// having_check) and as k_where.hip interprets it over a staged batch and
+// k_having.hip over a changelog segment (the interpreter itself: hsg_pred.h).
+// Not part of the ABI.
 #pragma once
 
 #include <string>
@@ -41,5 +43,58 @@ int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, 
 void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, WhereProg &out);
 
 void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a);
+
+// ---- HAVING pushdown (k_having.hip) ------------------------------------------
+// The same program over an op's changelog rows: column c is aggregate c of the
+// op (WhereProg::cols / f64 are 32-bit masks, kMaxAggs is 16).
+
+// Rows of one compaction tile (hsg_having_tile_rows).
+constexpr int kHavingTile = 256;
+
+// DevScalars::scratch word of the pass: bit 63 = the pass ran over the batch's
+// rows, the low bits = the rows it kept. A per-batch word (the clears zero
+// it): a batch whose kernels run more than once is filtered ahead of every
+// fetch of its scalars, and only the last fetch -- the batch's final rows --
+// is the one the host reads the word from (hsg_api.cpp push_sync). A fetch the
+// host will follow with another run of the batch (held back for table room,
+// late records under the optimistic path) finds the pass idle: k_having skips
+// when HavingArgs::skip or DevScalars::redo is set, so no row is filtered
+// twice, and the dropped-row count is taken from one pass. The same holds for
+// a fetch the host follows with the emit chain it had not launched
+// (HavingArgs::hold_emit, push_time_atomic): that chain appends behind the
+// rows the apply wrote, at their unfiltered count, so those rows stay where
+// they are until the chain has run.
+constexpr int kHavingWord = 7;
+constexpr uint64_t kHavingRan = 1ull << 63;
+// DevScalars::err bit: a tile waited past its bound for its predecessors
+constexpr uint32_t ERR_HAVING = 4u;
+
+struct HavingArgs {
+  OutCols out;             // the changelog columns (the op's own or the registered ones)
+  uint64_t base;           // first row of the batch's segment (the pending rows before it)
+  uint64_t max_rows;       // the host's bound on the segment (the tile states cover it)
+  int32_t n_aggs;
+  // the host did not launch the per-batch emit chain (it predicted a batch whose
+  // changelog the apply writes itself): when the batch filled the touched list
+  // after all, the host runs the chain after this fetch and fetches again, and
+  // the pass ahead of that fetch filters the whole segment
+  int32_t hold_emit;
+  // the segment's length: host_total unless it is UINT64_MAX, then
+  // *tot_a + *tot_b (tot_b may be null) as the batch's kernels left them
+  uint64_t host_total;
+  const uint64_t *tot_a, *tot_b;
+  const uint64_t *skip;    // non-zero: the batch will run again, leave the rows alone
+  uint64_t *state;         // [0] tile tickets, [2 ..] one word per tile; zeroed before the launch
+  DevScalars *sc;
+};
+
+// Type-check a HAVING program against the op's aggregate outputs (hsg_having_check).
+int having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg, std::string &err);
+// the value type of each aggregate output: COUNT_ALL / COUNT i64, AVG f64, else the column's
+void having_types(const hsg_op_config *cfg, int32_t *types);
+
+// words of HavingArgs::state for a segment of up to `rows` rows
+inline uint64_t having_state_words(uint64_t rows) { return ((rows / kHavingTile + 1 + 2) + 1) & ~1ull; }
+void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a);
 
 }  // namespace hsg

@@ -1,0 +1,232 @@
+// HAVING pushdown: the SQL filter over the changelog rows a batch appended.
+//
+// The reference chains genFilteRNodeFromHaving behind an unwindowed GROUP BY
+// (hstream-sql/src/HStream/SQL/Codegen.hs:524-529, :561-566): genFilterR over
+// each emitted record's aggregate object. Here that is one pass at the end of
+// a push over the segment [base, base + rows) of the op's changelog columns:
+// the op's postfix program (include/hstream_gpu.h hsg_where_ins, interpreted
+// by hsg_pred.h exactly as k_where.hip does) runs per row over the aggregate
+// columns it names, and the rows it keeps are compacted, in order, towards
+// `base` -- every column: key, window start / end, src_index, each aggregate
+// and the literal forms where kept.
+//
+// In place, one launch, a chained scan with look-back over tiles of
+// kHavingTile rows (one row per thread). A workgroup takes a tile ticket (tiles
+// are handed out in order, so a tile only ever waits for tiles already taken),
+// reads the named columns, evaluates, ranks its kept rows (wave ballots, a
+// scan of the wave counts in LDS), loads the other columns of the kept rows
+// only and parks the whole kept rows in LDS at their ranks. Then it publishes
+// its count, looks back for the sum of its predecessors' counts, publishes its
+// inclusive sum, and writes its rows from LDS, coalesced, to base + sum.
+//
+// The in-place hazard: a row's destination is never above its source, so a
+// tile writes onto rows of the tiles before it (and of itself). It is safe
+// because a tile publishes only after all its rows are in LDS -- the loads are
+// consumed by the LDS stores ahead of the workgroup barrier that precedes the
+// publication -- and writes only after its look-back found every predecessor
+// published (an inclusive sum stands for its publisher's predecessors too).
+// No tile reads a row another tile wrote in this launch, so the row loads need
+// no acquire; a tile's state is one 8-byte word (status and count together)
+// moved by relaxed agent-scope atomics, so there is no payload to order
+// behind a flag.
+//
+// Byte model, per row of the segment with c named columns, a aggregates and
+// f = 4 if the op keeps literal forms else 0:
+//   read    8 c                      every row (the named aggregate words)
+//   read    28 + f + 8 (a - c)       kept rows only (key, ws, we, src, the rest)
+//   written 28 + f + 8 a             kept rows only
+// plus 8 B of tile state per 256 rows each way and one ticket atomic per tile.
+// Flags: none are stored (a row's keep bit lives in a ballot). LDS: 40 KiB per
+// workgroup (256 rows of 160 B), three workgroups per CU.
+#include "hsg_pred.h"
+
+namespace hsg {
+
+namespace {
+
+constexpr int T = kHavingTile;
+constexpr int kWaves = T / 64;
+constexpr uint64_t kStAgg = 1ull << 62, kStSum = 2ull << 62, kStMask = 3ull << 62;
+// polls of a predecessor before a tile gives up (ERR_HAVING): a tile's work is
+// tens of microseconds, a poll about one
+constexpr uint32_t kMaxPolls = 1u << 20;
+// look_back's answer then: the tile has no offset, so it writes no row and
+// publishes no sum, and its workgroup takes no further tile (the tiles behind
+// it give up the same way; the push fails with ERR_HAVING and counts no row)
+constexpr uint64_t kNoSum = ~0ull;
+
+__device__ __forceinline__ uint64_t st_load(const uint64_t *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_store(uint64_t *p, uint64_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Wave 0 of tile t: the kept rows of tiles [0, t). Lane l reads the state of
+// tile t - 1 - l (64 predecessors a round); the round ends at the nearest
+// inclusive sum once every tile between it and t has published.
+__device__ __forceinline__ uint64_t look_back(const uint64_t *tiles, uint64_t t, DevScalars *sc) {
+  const int lane = threadIdx.x & 63;
+  uint64_t excl = 0;
+  uint64_t hi = t;  // this round reads tiles hi - 1 - lane
+  uint32_t polls = 0;
+  while (true) {
+    const bool real = (uint64_t)lane < hi;
+    // before tile 0: an inclusive sum of 0
+    const uint64_t w = real ? st_load(tiles + (hi - 1 - lane)) : kStSum;
+    const uint64_t stat = w & kStMask;
+    const uint64_t sums = __ballot(stat == kStSum);
+    const int first = sums ? __builtin_ctzll(sums) : 64;
+    const uint64_t need = first >= 63 ? ~0ull : ((2ull << first) - 1);
+    const uint64_t missing = __ballot(stat == 0) & need;
+    if (missing) {
+      if (++polls > kMaxPolls) {
+        if (lane == 0) atomicOr(&sc->err, ERR_HAVING);
+        return kNoSum;
+      }
+      __builtin_amdgcn_s_sleep(2);
+      continue;
+    }
+    excl += wave_sum(lane <= first ? (w & ~kStMask) : 0);
+    if (first < 64) return excl;
+    hi -= 64;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArgs a) {
+  __shared__ uint64_t s_w[3 + kMaxAggs][T];  // ws, we, src, aggregates
+  __shared__ uint32_t s_key[T], s_form[T];
+  __shared__ uint32_t s_wcnt[kWaves];
+  __shared__ uint64_t s_tile, s_excl;
+
+  uint64_t total = a.host_total;
+  if (total == UINT64_MAX) total = *a.tot_a + (a.tot_b ? *a.tot_b : 0);
+  if (total > a.max_rows) {
+    // the tile states cover max_rows, and the room check holds the rows below it
+    total = a.max_rows;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.sc->err, ERR_HAVING);
+  }
+  // the host's own condition for running the emit chain it had not launched
+  // (push_time_atomic, after this fetch): the batch filled the touched list
+  // and had no error; the chain appends at the unfiltered count of the rows
+  // the apply wrote (scratch[3]), and the pass ahead of the next fetch filters
+  // all of them (uniform: the batch's kernels have finished, and the bit this
+  // kernel sets is left out)
+  const uint64_t how = a.sc->scratch[2];
+  const bool emit_follows = a.hold_emit && how != 1 && how != 3 && (a.sc->scratch[1] | a.sc->scratch[6]) != 0 &&
+                            (a.sc->err & (ERR_OOM | ERR_RANGE)) == 0;
+  if (*a.skip || a.sc->redo || emit_follows || total == 0) {
+    // nothing to filter, or rows the batch's next run writes again or appends to
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.sc->scratch[kHavingWord] = total == 0 ? kHavingRan : 0;
+    return;
+  }
+  const uint64_t n_tiles = (total + T - 1) / T;
+  uint64_t *ticket = a.state, *tiles = a.state + 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  while (true) {
+    if (tid == 0) s_tile = atomicAdd((unsigned long long *)ticket, 1ull);
+    __syncthreads();
+    const uint64_t t = s_tile;
+    if (t >= n_tiles) return;
+    const uint64_t row = t * T + tid;
+    const bool in = row < total;
+    const uint64_t src = a.base + row;
+
+    // the named aggregate words, all loads in flight before the program runs
+    uint64_t cv[kMaxAggs];
+    uint32_t absent = 0;
+#pragma unroll
+    for (int c = 0; c < kMaxAggs; ++c) cv[c] = (in && ((p.cols >> c) & 1u)) ? (uint64_t)a.out.agg[c][src] : 0;
+    // an f64 output that is NaN (AVG of no value) is the error value
+#pragma unroll
+    for (int c = 0; c < kMaxAggs; ++c) {
+      const double d = pred::as_f64(cv[c]);
+      if (((p.cols & p.f64) >> c) & 1u) absent |= d != d ? 1u << c : 0u;
+    }
+    const bool keep = in && pred::eval(p, cv, absent);
+
+    // rank among the tile's kept rows
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_wcnt[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, count = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      before += w < wave ? s_wcnt[w] : 0;
+      count += s_wcnt[w];
+    }
+    const uint32_t r = before + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+
+    // the kept rows, whole, into LDS at their ranks: every load of the other
+    // columns in flight first, then the LDS stores
+    if (keep) {
+      const uint32_t k = a.out.key[src];
+      const int64_t ws = a.out.ws[src], we = a.out.we[src], si = a.out.src[src];
+      const uint32_t fm = a.out.form ? a.out.form[src] : 0;
+#pragma unroll
+      for (int c = 0; c < kMaxAggs; ++c)
+        if (c < a.n_aggs && !((p.cols >> c) & 1u)) cv[c] = (uint64_t)a.out.agg[c][src];
+      s_key[r] = k;
+      s_w[0][r] = (uint64_t)ws;
+      s_w[1][r] = (uint64_t)we;
+      s_w[2][r] = (uint64_t)si;
+#pragma unroll
+      for (int c = 0; c < kMaxAggs; ++c)
+        if (c < a.n_aggs) s_w[3 + c][r] = cv[c];
+      if (a.out.form) s_form[r] = fm;
+    }
+    // every load of the tile's rows has landed (the LDS stores consumed them)
+    __syncthreads();
+
+    if (wave == 0) {
+      if (lane == 0) st_store(tiles + t, kStAgg | count);
+      const uint64_t excl = look_back(tiles, t, a.sc);
+      if (lane == 0) {
+        s_excl = excl;
+        if (excl != kNoSum) {
+          st_store(tiles + t, kStSum | (excl + count));
+          if (t == n_tiles - 1) a.sc->scratch[kHavingWord] = kHavingRan | (excl + count);
+        }
+      }
+    }
+    __syncthreads();
+    if (s_excl == kNoSum) return;  // uniform
+
+    // every predecessor has its rows in LDS or written: write ours
+    if ((uint32_t)tid < count) {
+      const uint64_t dst = a.base + s_excl + tid;
+      a.out.key[dst] = s_key[tid];
+      a.out.ws[dst] = (int64_t)s_w[0][tid];
+      a.out.we[dst] = (int64_t)s_w[1][tid];
+      a.out.src[dst] = (int64_t)s_w[2][tid];
+#pragma unroll
+      for (int c = 0; c < kMaxAggs; ++c)
+        if (c < a.n_aggs) a.out.agg[c][dst] = (int64_t)s_w[3 + c][tid];
+      if (a.out.form) a.out.form[dst] = s_form[tid];
+    }
+    __syncthreads();  // LDS and s_tile are reused by the next tile
+  }
+}
+
+void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a) {
+  if (!p.n || !a.max_rows) return;
+  // a workgroup per tile of the host's bound, at most one resident round (three
+  // workgroups per CU by LDS); the workgroups take tiles until none is left, so
+  // the grid bounds nothing but the parallelism
+  uint64_t g = (a.max_rows + T - 1) / T;
+  if (g > 768) g = 768;
+  hipLaunchKernelGGL(k_having, dim3((unsigned)g), dim3(T), 0, s, p, a);
+}
+
+}  // namespace hsg
+
+extern "C" int hsg_having_tile_rows(void) { return hsg::kHavingTile; }

@@ -12,72 +12,14 @@
 // Per record the pass moves the key in and out (4 + 4 B) and, of the columns
 // the program names only, the value and the valid byte (9 B):
 //   bytes = N * (8 + 9 * named columns).
-// The program arrives as a kernel argument, so opcodes, column numbers and
-// the value types (static: column type or constant kind) live in scalar
-// registers and every branch over them is uniform across the wave. The
-// operand stack is eight named entries shifted on push / pop -- constant
-// indices only, so it stays in vector registers (no scratch) -- and the
-// three-valued logic is a per-lane error bit beside each entry.
-#include "hsg_where.h"
+// The program arrives as a kernel argument and is interpreted by hsg_pred.h
+// (shared with the HAVING pass, k_having.hip): scalar opcodes, a register
+// stack, a per-lane error bit beside each entry.
+#include "hsg_pred.h"
 
 namespace hsg {
 
 constexpr int kWhereThreads = 256;
-
-namespace {
-
-constexpr int D = HSG_WHERE_MAX_DEPTH;
-
-// The operand stack: v[0] is the top. Values are i64 or f64 bits, bools 0 / 1.
-// err: bit k = entry k is the error value (per lane); f: bit k = entry k is
-// f64 (uniform: derived from the program alone).
-struct Stack {
-  uint64_t v[D];
-  uint32_t err;
-  uint32_t f;
-  __device__ __forceinline__ void push(uint64_t x, bool e, bool isf) {
-#pragma unroll
-    for (int k = D - 1; k > 0; --k) v[k] = v[k - 1];
-    v[0] = x;
-    err = (err << 1) | (e ? 1u : 0u);
-    f = (f << 1) | (isf ? 1u : 0u);
-  }
-  __device__ __forceinline__ void pop() {
-#pragma unroll
-    for (int k = 0; k < D - 1; ++k) v[k] = v[k + 1];
-    err >>= 1;
-    f >>= 1;
-  }
-};
-
-__device__ __forceinline__ double as_f64(uint64_t u) { return __builtin_bit_cast(double, u); }
-__device__ __forceinline__ uint64_t as_u64(double d) { return __builtin_bit_cast(uint64_t, d); }
-
-// Ordering of two values as Scientific orders them: -1 / 0 / 1, 2 = unordered
-// (a NaN, which no JSON number is). An i64 against an f64 is compared exactly:
-// the integer is never rounded to a double (2^53 + 1 > 9007199254740992.0,
-// INT64_MAX < 2^63).
-__device__ __forceinline__ int cmp_i_f(int64_t i, double d) {
-  if (d != d) return 2;
-  if (d >= 9223372036854775808.0) return -1;
-  if (d < -9223372036854775808.0) return 1;
-  const double t = __builtin_trunc(d);  // |t| <= 2^63, exact as an i64 unless t = -2^63 (also exact)
-  const int64_t ti = (int64_t)t;
-  if (i != ti) return i < ti ? -1 : 1;
-  return d > t ? -1 : (d < t ? 1 : 0);
-}
-__device__ __forceinline__ int cmp_vals(uint64_t a, bool af, uint64_t b, bool bf) {
-  if (!af && !bf) return (int64_t)a < (int64_t)b ? -1 : ((int64_t)a > (int64_t)b ? 1 : 0);
-  if (af && bf) {
-    const double x = as_f64(a), y = as_f64(b);
-    return x < y ? -1 : (x > y ? 1 : (x == y ? 0 : 2));
-  }
-  if (!af) return cmp_i_f((int64_t)a, as_f64(b));
-  const int c = cmp_i_f((int64_t)b, as_f64(a));
-  return c == 2 ? 2 : -c;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, const WhereArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kWhereThreads;
@@ -100,79 +42,7 @@ __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, cons
         if (in && a.valid[c] && !(a.valid[c][i] & 1u)) absent |= 1u << c;
       }
     }
-    Stack st;
-#pragma unroll
-    for (int k = 0; k < D; ++k) st.v[k] = 0;
-    st.err = 0;
-    st.f = 0;
-    for (int pc = 0; pc < p.n; ++pc) {
-      const int32_t op = p.ins[pc].op;
-      if (op == HSG_W_COL) {
-        const int32_t c = p.ins[pc].arg;
-        uint64_t x = 0;
-#pragma unroll
-        for (int k = 0; k < kMaxCols; ++k) x = c == k ? cv[k] : x;
-        st.push(x, (absent >> c) & 1u, (p.f64 >> c) & 1u);
-      } else if (op == HSG_W_I64 || op == HSG_W_F64) {
-        st.push((uint64_t)p.ins[pc].imm.i, false, op == HSG_W_F64);
-      } else if (op <= HSG_W_MUL) {
-        // value value -> value: i64 wraps, anything with an f64 is f64
-        const uint64_t r = st.v[0], l = st.v[1];
-        const bool rf = st.f & 1u, lf = (st.f >> 1) & 1u;
-        const bool e = (st.err & 3u) != 0;
-        uint64_t o;
-        if (!lf && !rf) {
-          o = op == HSG_W_ADD ? l + r : (op == HSG_W_SUB ? l - r : l * r);
-        } else {
-          const double x = lf ? as_f64(l) : (double)(int64_t)l, y = rf ? as_f64(r) : (double)(int64_t)r;
-          o = as_u64(op == HSG_W_ADD ? x + y : (op == HSG_W_SUB ? x - y : x * y));
-        }
-        st.pop();
-        st.pop();
-        st.push(o, e, lf || rf);
-      } else if (op <= HSG_W_GE) {
-        // value value -> bool; error if either operand is
-        const int c = cmp_vals(st.v[1], (st.f >> 1) & 1u, st.v[0], st.f & 1u);
-        const bool e = (st.err & 3u) != 0;
-        bool o;
-        switch (op) {
-          case HSG_W_EQ: o = c == 0; break;
-          case HSG_W_NE: o = c != 0; break;
-          case HSG_W_LT: o = c == -1; break;
-          case HSG_W_GT: o = c == 1; break;
-          case HSG_W_LE: o = c == -1 || c == 0; break;
-          default: o = c == 1 || c == 0; break;
-        }
-        st.pop();
-        st.pop();
-        st.push(o ? 1 : 0, e, false);
-      } else if (op == HSG_W_BETWEEN) {
-        // lo x hi (Codegen.hs:331-341): lo > x decides before hi is looked at
-        const int c1 = cmp_vals(st.v[2], (st.f >> 2) & 1u, st.v[1], (st.f >> 1) & 1u);
-        const int c2 = cmp_vals(st.v[1], (st.f >> 1) & 1u, st.v[0], st.f & 1u);
-        const bool e_lox = (st.err & 6u) != 0, e_hi = (st.err & 1u) != 0;
-        const bool gt1 = c1 == 1;
-        const bool e = e_lox || (!gt1 && e_hi);
-        const bool o = !gt1 && c2 != 1 && c1 != 2 && c2 != 2;
-        st.pop();
-        st.pop();
-        st.pop();
-        st.push(o ? 1 : 0, e, false);
-      } else if (op == HSG_W_NOT) {
-        st.v[0] ^= 1ull;  // NOT(error) = error: the bit stays
-      } else {
-        // AND / OR over (l, r), both computed: l decides when it is false
-        // (AND) / true (OR) or the error; else the result is r
-        const bool l = st.v[1] != 0, r = st.v[0] != 0;
-        const bool le = (st.err >> 1) & 1u, re = st.err & 1u;
-        const bool take_l = le || (op == HSG_W_AND ? !l : l);
-        const bool o = take_l ? l : r, e = take_l ? le : re;
-        st.pop();
-        st.pop();
-        st.push(o ? 1 : 0, e, false);
-      }
-    }
-    const bool keep = st.v[0] != 0 && !(st.err & 1u);
+    const bool keep = pred::eval(p, cv, absent);
     const bool drop = key != HSG_KEY_NONE && !keep;
     if (in) a.out[i] = drop ? HSG_KEY_NONE : key;
     const uint64_t m = __ballot(drop);

@@ -425,6 +425,9 @@ void op_device_free(OpDevice &d) {
   if (d.tkeys) hipFree(d.tkeys);
   d.tkeys = nullptr;
   d.tkeys_cap = 0;
+  if (d.hv_state) hipFree(d.hv_state);
+  d.hv_state = nullptr;
+  d.hv_state_words = 0;
   if (d.xsend) hipFree(d.xsend);
   if (d.xrecv) hipFree(d.xrecv);
   d.xsend = d.xrecv = nullptr;
@@ -725,6 +728,10 @@ int clear_batch_scalars(OpDevice &d, std::string &err) {
 }
 
 static int status_from_err(uint32_t e, std::string &err) {
+  if (e & ERR_HAVING) {
+    err = "having: the changelog filter did not complete (internal)";
+    return HSG_E_DEVICE;
+  }
   if (e & ERR_OOM) {
     err = "HBM state table / arena full (raise state_capacity)";
     return HSG_E_OOM;
@@ -736,10 +743,53 @@ static int status_from_err(uint32_t e, std::string &err) {
   return HSG_OK;
 }
 
+// The HAVING pass over the rows the batch appended (k_having.hip), enqueued
+// ahead of the fetch that reads the batch's scalars: no round trip of its own.
+// The rows' count is on the device (or in hv.host_total); the grid and the
+// tile states are sized from the host's bound.
+static int having_pass(OpDevice &d, std::string &err) {
+  const uint64_t room = d.out_cap > d.hv.pending ? d.out_cap - d.hv.pending : 0;
+  uint64_t rows = d.hv.host_total != UINT64_MAX ? d.hv.host_total : d.hv.bound;
+  if (rows > room) rows = room;
+  if (!rows) return HSG_OK;
+  const uint64_t words = having_state_words(rows);
+  if (words > d.hv_state_words) {
+    if (d.hv_state) hipFree(d.hv_state);
+    d.hv_state = nullptr;
+    d.hv_state_words = 0;
+    const uint64_t want = words > 2 * 1024 ? 2 * words : 2 * 1024;
+    DTRY(hipMalloc((void **)&d.hv_state, want * sizeof(uint64_t)));
+    d.hv_state_words = want;
+  }
+  DTRY(hipMemsetAsync(d.hv_state, 0, words * sizeof(uint64_t), d.stream));
+  HavingArgs h;
+  memset(&h, 0, sizeof(h));
+  h.out = d.out;
+  h.base = d.hv.pending;
+  h.max_rows = rows;
+  h.n_aggs = d.hv.n_aggs;
+  h.host_total = d.hv.host_total;
+  h.tot_a = d.hv.dev_total ? d.hv.dev_total : &d.sc->out_rows;
+  h.tot_b = d.hv.dev_total ? nullptr : &d.sc->scratch[3];
+  h.skip = d.hv.skip ? d.hv.skip : &d.sc->scratch[32];
+  h.hold_emit = d.hv.hold_emit ? 1 : 0;
+  h.state = d.hv_state;
+  h.sc = d.sc;
+  launch_having(d.stream, d.having, h);
+  DTRY(hipGetLastError());
+  return HSG_OK;
+}
+
 int finish_batch(OpDevice &d, int64_t wm_in, uint64_t n, PushResult &r, std::string &err) {
-  int rc = fetch_scalars(d, err);
+  int rc = d.having.n ? having_pass(d, err) : HSG_OK;
+  if (rc != HSG_OK) return rc;
+  rc = fetch_scalars(d, err);
   if (rc != HSG_OK) return rc;
   const DevScalars &s = *d.h_sc;
+  if (d.having.n) {
+    d.hv_ran = (s.scratch[kHavingWord] & kHavingRan) != 0;
+    d.hv_kept = s.scratch[kHavingWord] & ~kHavingRan;
+  }
 #ifndef HSG_PHASE_CLOCKS
 #define HSG_PHASE_CLOCKS 0
 #endif
@@ -897,6 +947,8 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
                        (uint64_t *)&d.sc->out_rows);
       }
     }
+    // (the HAVING pass stays idle ahead of a fetch the emit chain below follows)
+    d.hv.hold_emit = skipped_emit;
     // ev_a .. ev_b: the batch's device pipeline (aggregation + changelog rows)
     DTRY(hipEventRecord(d.ev_b, d.stream));
     DTRY(hipGetLastError());
@@ -1037,6 +1089,7 @@ static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program
     d.sc_clean = false;
     launch_part_emit(d.stream, d.tw, prog, p, d.part, d.out, a.pending, d.out_cap, d.sc);
     DTRY(hipEventRecord(d.ev_b, d.stream));
+    d.hv.hold_emit = false;  // the batch's final rows: the apply's own and the chain's
     rc = finish_batch(d, a.wm_in, kb.n, r1, err);
     r.out_rows = r1.out_rows;
     if (rc != HSG_OK) return rc;
@@ -1078,6 +1131,7 @@ int op_push(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const Pu
             std::string &err) {
   const hsg_batch *b = a.batch;
   d.where_staged = nullptr;  // a new push: stage_batch filters it
+  d.hv_ran = false;
   // room in the table for the batch's worst case (sharded ops: in push_local,
   // once the records this rank owns are known)
   if (!a.comm) {
@@ -1109,6 +1163,16 @@ int op_push(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const Pu
 // watermark it saw in the global arrival order (computed before the exchange).
 int push_local(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const PushArgs &a, const Batch &kb,
                const int64_t *seq, const int64_t *rec_wm, PushResult &r, std::string &err) {
+  if (d.having.n) {
+    // the segment the HAVING pass filters: this rank's rows of this batch
+    // (the paths that count their rows elsewhere say so before they finish)
+    d.hv.pending = a.pending;
+    d.hv.bound = kb.n * d.wpr;
+    d.hv.host_total = UINT64_MAX;
+    d.hv.dev_total = nullptr;
+    d.hv.skip = nullptr;
+    d.hv.hold_emit = false;
+  }
   if (cfg.window_kind == HSG_SESSION) return push_session(d, cfg, prog, a, kb, seq, r, err);
   if (a.comm) {
     int rc = tw_maintain(d, cfg, prog, kb.n, a.wm_in, a.pending, err);

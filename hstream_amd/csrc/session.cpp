@@ -390,6 +390,8 @@ static int push_session_bucket(OpDevice &d, const hsg_op_config &cfg, const Prog
   DTRY(hipEventRecord(d.ev_b, d.stream));
   DTRY(hipGetLastError());
   done = true;
+  // (the HAVING pass: the per-record rows' count is in the store's bookkeeping)
+  if (cfg.emit_mode == HSG_EMIT_PER_RECORD) d.hv.dev_total = d.ss.meta + M_BRROWS;
   int rc = finish_session_batch(d, a.wm_in, n, r, err);
   const uint64_t V = d.h_meta[M_BRROWS];
   if (cfg.emit_mode == HSG_EMIT_PER_RECORD) r.out_rows = V;
@@ -429,6 +431,7 @@ static int push_session_replay(OpDevice &d, const hsg_op_config &cfg, const Prog
   *v32 = (uint32_t)V;
   DTRY(hipMemcpyAsync(pb.runs + R, v32, sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
   int rc = HSG_OK;
+  if (cfg.emit_mode == HSG_EMIT_PER_RECORD) d.hv.host_total = V;  // (the HAVING pass: rows [pending, pending + V))
   for (int attempt = 0;; ++attempt) {
     launch_ss_replay_need(d.stream, d.ss, slot, pb.runs, R);
     launch_ss_process(d.stream, kb, sp, d.ss, prog, slot, ridx, pb.runs, R, pb.off, seq, d.out, a.pending, d.sc);
@@ -460,6 +463,8 @@ int push_session(OpDevice &d, const hsg_op_config &cfg, const Program &prog, con
   int rc = clear_batch_scalars(d, err);
   if (rc != HSG_OK) return rc;
   if (!kb.n) return finish_batch(d, a.wm_in, 0, r, err);
+  // (the HAVING pass leaves the rows of a pass the arena stopped short: it runs again)
+  d.hv.skip = d.ss.meta + M_FAIL;
   rc = ensure_keys(d, kb.n, err);
   if (rc != HSG_OK) return rc;
   // per-batch words: need, fail, touched list, groups, runs, big buckets

@@ -246,6 +246,7 @@ int push_time_perrecord(OpDevice &d, const hsg_op_config &cfg, const Program &pr
     DTRY(hipEventRecord(d.ev_b, d.stream));
     DTRY(hipGetLastError());
   }
+  d.hv.host_total = P;  // (the rows are [pending, pending + P); this path counts them on the host)
   rc = finish_batch(d, a.wm_in, kb.n, r, err);
   r.out_rows = P;
   if (kb.n) {

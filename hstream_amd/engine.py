@@ -45,6 +45,13 @@ def load_library(path=LIB_PATH):
     L.hsg_where_check.restype = C.c_int
     L.hsg_op_create_where.argtypes = [vp, P(abi.hsg_op_config), P(abi.hsg_where_ins), C.c_int32, P(vp)]
     L.hsg_op_create_where.restype = C.c_int
+    L.hsg_having_check.argtypes = [P(abi.hsg_where_ins), C.c_int32, P(abi.hsg_op_config), C.c_char_p, C.c_size_t]
+    L.hsg_having_check.restype = C.c_int
+    L.hsg_op_create_filtered.argtypes = [vp, P(abi.hsg_op_config), P(abi.hsg_where_ins), C.c_int32,
+                                         P(abi.hsg_where_ins), C.c_int32, P(vp)]
+    L.hsg_op_create_filtered.restype = C.c_int
+    L.hsg_having_tile_rows.argtypes = []
+    L.hsg_having_tile_rows.restype = C.c_int
     L.hsg_op_stats.argtypes = [vp, P(abi.hsg_stats)]
     L.hsg_op_stats.restype = C.c_int
     L.hsg_op_set_changelog.argtypes = [vp, P(abi.hsg_rows)]
@@ -91,6 +98,22 @@ def where_check(program, col_types):
     buf = C.create_string_buffer(256)
     rc = L.hsg_where_check(prog, n, types, len(col_types), buf, len(buf))
     return rc, buf.value.decode()
+
+
+def having_check(program, spec: OpSpec):
+    """hsg_having_check (host only, no GPU): (status, message) for a HAVING
+    program over the aggregate outputs of the op `spec` describes."""
+    L = load_library()
+    prog, n = abi.where_array(program)
+    cfg, keep = spec.to_config()
+    buf = C.create_string_buffer(256)
+    rc = L.hsg_having_check(prog, n, C.byref(cfg), buf, len(buf))
+    return rc, buf.value.decode()
+
+
+def having_tile_rows() -> int:
+    """Rows of one compaction tile of the HAVING pass (hsg_having_tile_rows)."""
+    return load_library().hsg_having_tile_rows()
 
 
 def comm_unique_id() -> bytes:
@@ -154,10 +177,11 @@ class GpuOp(OpHandle):
         cfg, keep = spec.to_config()
         h = C.c_void_p()
         what = "hsg_op_create"
-        if spec.where is not None:
-            what = "hsg_op_create_where"
-            prog, n = abi.where_array(spec.where)
-            rc = engine._lib.hsg_op_create_where(engine._h, C.byref(cfg), prog, n, C.byref(h))
+        if spec.having is not None or spec.where is not None:
+            what = "hsg_op_create_filtered"
+            wprog, wn = abi.where_array(spec.where) if spec.where is not None else (None, 0)
+            hprog, hn = abi.where_array(spec.having) if spec.having is not None else (None, 0)
+            rc = engine._lib.hsg_op_create_filtered(engine._h, C.byref(cfg), wprog, wn, hprog, hn, C.byref(h))
         else:
             rc = engine._lib.hsg_op_create(engine._h, C.byref(cfg), C.byref(h))
         if rc != abi.HSG_OK:

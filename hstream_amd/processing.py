@@ -211,6 +211,18 @@ class Where:
 
 
 @dataclass
+class Having:
+    """The query's HAVING clause for an aggregate: the refined search condition
+    (hstream_amd.sql RCond*) over the aggregates' aliases. The op runs it on the
+    GPU over the changelog rows it emits and forwards the rows it keeps, where
+    the reference chains genFilteRNodeFromHaving behind an unwindowed
+    aggregate (Codegen.hs:524-529); the table's state (dump, view reads) is
+    that of the aggregate without it."""
+
+    cond: Any
+
+
+@dataclass
 class Materialized:
     """mKeySerde/mValueSerde/mStateStore (Stream/Internal.hs:123-128): the key
     dictionary plays the key serde, the HBM table the state store."""
@@ -237,8 +249,8 @@ class GroupedStream:
         return SessionWindowedStream(self, windows)
 
     def aggregate(self, aggs: Sequence[Agg], materialized: Materialized, emit=abi.HSG_EMIT_PER_RECORD,
-                  where: Optional[Where] = None) -> "Table":
-        return Table(self, OpSpec(abi.HSG_UNWINDOWED, emit), aggs, materialized, where)
+                  where: Optional[Where] = None, having: Optional[Having] = None) -> "Table":
+        return Table(self, OpSpec(abi.HSG_UNWINDOWED, emit), aggs, materialized, where, having)
 
     def count(self, materialized: Materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -253,11 +265,12 @@ class TimeWindowedStream:
         self.grouped = grouped
         self.windows = windows
 
-    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None) -> "Table":
+    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None,
+                  having: Optional[Having] = None) -> "Table":
         w = self.windows
         kind = abi.HSG_TUMBLING if w.twAdvanceMs == w.twSizeMs else abi.HSG_HOPPING
         spec = OpSpec(kind, emit, size_ms=w.twSizeMs, advance_ms=w.twAdvanceMs, grace_ms=w.twGraceMs)
-        return Table(self.grouped, spec, aggs, materialized, where)
+        return Table(self.grouped, spec, aggs, materialized, where, having)
 
     def count(self, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -268,9 +281,10 @@ class SessionWindowedStream:
         self.grouped = grouped
         self.windows = windows
 
-    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None) -> "Table":
+    def aggregate(self, aggs, materialized, emit=abi.HSG_EMIT_PER_RECORD, where: Optional[Where] = None,
+                  having: Optional[Having] = None) -> "Table":
         spec = OpSpec(abi.HSG_SESSION, emit, gap_ms=self.windows.swInactivityGap)
-        return Table(self.grouped, spec, aggs, materialized, where)
+        return Table(self.grouped, spec, aggs, materialized, where, having)
 
     def count(self, materialized, emit=abi.HSG_EMIT_PER_RECORD) -> "Table":
         return self.aggregate([COUNT_ALL("count")], materialized, emit)
@@ -284,7 +298,7 @@ class Table:
     them (per-record mode) or one row per touched group (per-batch mode)."""
 
     def __init__(self, grouped: GroupedStream, spec: OpSpec, aggs: Sequence[Agg], materialized: Materialized,
-                 where: Optional[Where] = None):
+                 where: Optional[Where] = None, having: Optional[Having] = None):
         self.grouped = grouped
         self.aggs = list(aggs)
         self.mat = materialized
@@ -313,6 +327,12 @@ class Table:
                     fields.append((f, f in where.float_fields))
                     self.numeric.append(True)
             spec.where = sql.compile_where(where.cond, names, key_field=grouped.key_field)
+        self.having = having
+        if having is not None:
+            # the filter over the emitted rows runs in the op too
+            # (hsg_op_create_filtered), over the aggregates by alias
+            from . import sql
+            spec.having = sql.compile_having(having.cond, self.aggs)
         self.fields = fields
         self._decoder = None
         spec.col_types = [abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in fields]

@@ -17,6 +17,10 @@ the BNFC parser/validator are out of scope).
                      the GPU ahead of the aggregate (include/hstream_gpu.h
                      hsg_where_ins), where the reference chains genFilterNode
                      in front of it (Codegen.hs:540)
+  compile_having     the HAVING condition as the same program over the
+                     aggregates' aliases, run over the rows the op emits,
+                     where the reference chains genFilteRNodeFromHaving
+                     behind an unwindowed aggregate (Codegen.hs:524-529)
 """
 import math
 from dataclasses import dataclass
@@ -232,7 +236,7 @@ def where_fields(cond) -> List[str]:
     return out
 
 
-def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None) -> List[Tuple]:
+def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, what: str = "WHERE") -> List[Tuple]:
     """The condition as a postfix hsg_where_ins program, [(op,) | (op, arg)],
     over value columns named `fields` (column c = fields[c]). ValueError for
     what the program cannot say -- string / bool / null constants, a predicate
@@ -246,9 +250,10 @@ def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None) 
         if isinstance(e, RExprCol):
             name = _field_name(e)
             if key_field is not None and name == key_field:
-                raise ValueError(f"WHERE on the group key {name!r} is not pushed down")
+                raise ValueError(f"{what} on the group key {name!r} is not pushed down")
             if name not in fields:
-                raise ValueError(f"WHERE reads {name!r}, which is not a value column")
+                raise ValueError(f"{what} reads {name!r}, which is not " +
+                                 ("a value column" if what == "WHERE" else "an alias of the SELECT list"))
             prog.append((abi.HSG_W_COL, fields.index(name)))
             return 1
         if isinstance(e, RExprConst):
@@ -302,10 +307,26 @@ def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None) 
 
     depth = search(cond)
     if len(prog) > abi.HSG_WHERE_MAX_INS:
-        raise ValueError(f"WHERE needs {len(prog)} instructions (max {abi.HSG_WHERE_MAX_INS})")
+        raise ValueError(f"{what} needs {len(prog)} instructions (max {abi.HSG_WHERE_MAX_INS})")
     if depth > abi.HSG_WHERE_MAX_DEPTH:
-        raise ValueError(f"WHERE needs a stack of {depth} (max {abi.HSG_WHERE_MAX_DEPTH})")
+        raise ValueError(f"{what} needs a stack of {depth} (max {abi.HSG_WHERE_MAX_DEPTH})")
     return prog
+
+
+def compile_having(cond, aggs: Sequence) -> List[Tuple]:
+    """The HAVING condition as the same postfix program over the op's
+    aggregate outputs: column j is aggs[j] (P.Agg, or its alias), named by
+    alias as the reference's filter reads the emitted object (genFilterR over
+    {alias: Number}, Codegen.hs:524-529). The group key can be named only
+    where it is also a SELECT passthrough (a LAST aggregate with that alias):
+    no key-field rule. ValueError for a name that is no alias -- every record
+    would throw in the reference -- for duplicate aliases, and for what
+    compile_where cannot say; such a HAVING is not pushed down."""
+    aliases = [a if isinstance(a, str) else a.alias for a in aggs]
+    dup = sorted({a for a in aliases if aliases.count(a) > 1})
+    if dup:
+        raise ValueError(f"HAVING over duplicate aliases {dup} is not pushed down")
+    return compile_where(cond, aliases, what="HAVING")
 
 
 # SELECT items: ("COUNT(*)",) / ("COUNT", col) / ("SUM", col) / ("MIN", col) /
@@ -346,11 +367,18 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=()) -> List[P.Agg]
 
 
 def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.HSG_EMIT_PER_RECORD,
-                      float_fields=(), state_capacity=0, where=None) -> P.Table:
+                      float_fields=(), state_capacity=0, where=None, having=None) -> P.Table:
     """genGroupByNode: groupBy -> (timeWindowedBy | sessionWindowedBy)? -> aggregate.
     where: the query's RSearchCond, run by the op on the GPU where the
     reference chains genFilterNode in front (Codegen.hs:540); ValueError when
-    compile_where cannot express it (the caller then filters upstream)."""
+    compile_where cannot express it (the caller then filters upstream).
+    having: the query's HAVING condition over the SELECT aliases, run by the
+    op over the changelog rows it emits where the reference chains
+    genFilteRNodeFromHaving behind the aggregate (Codegen.hs:524-529, :561-566);
+    ValueError when compile_having cannot express it. As in the reference, it
+    applies to an unwindowed GROUP BY only: for a windowed query (Codegen.hs:
+    554-559 never looks at it) and for HSG_EMIT_NONE, which emits nothing, it
+    is dropped silently."""
     grouped = P.groupBy(engine, group_by.column)
     aggs = gen_aggregate_components(sel, float_fields)
     mat = P.Materialized(state_capacity=state_capacity)
@@ -358,7 +386,8 @@ def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.H
         where = P.Where(where, float_fields)
     w = group_by.window
     if w is None:
-        return grouped.aggregate(aggs, mat, emit, where=where)
+        hv = P.Having(having) if having is not None and emit != abi.HSG_EMIT_NONE else None
+        return grouped.aggregate(aggs, mat, emit, where=where, having=hv)
     if isinstance(w, RTumblingWindow):
         return grouped.timeWindowedBy(P.mkTumblingWindow(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit,
                                                                                                where=where)

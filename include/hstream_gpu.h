@@ -97,7 +97,8 @@ enum hsg_agg_kind {
   HSG_SUM       = 2, /* SUM(col)   Codegen.hs:423-435                                        */
   HSG_MIN       = 3, /* MIN(col)   Codegen.hs:449-461, identity maxBound::Int                */
   HSG_MAX       = 4, /* MAX(col)   Codegen.hs:436-448, identity minBound::Int                */
-  HSG_AVG       = 5, /* SUM(col)/COUNT(col) as f64 (NaN when COUNT(col) = 0)                 */
+  HSG_AVG       = 5, /* SUM(col)/COUNT(col) as f64 (NaN when COUNT(col) = 0; a HAVING program
+                        reads that NaN as its error value, see "HAVING pushdown" below)      */
   HSG_LAST      = 6  /* non-aggregate SELECT column, Codegen.hs:463-469 (time windows and
                         unwindowed only)                                                     */
 };
@@ -166,6 +167,36 @@ enum hsg_where_opcode {
 typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } hsg_where_ins;
 #define HSG_WHERE_MAX_INS   64
 #define HSG_WHERE_MAX_DEPTH 8
+
+/* HAVING pushdown: the same program over the rows an op emits. The reference
+ * chains genFilteRNodeFromHaving behind an unwindowed GROUP BY (Codegen.hs:
+ * 524-529, :561-566): genFilterR over each emitted record's aggregate object
+ * {alias: Number}. Here the op filters, at the end of every push, the changelog
+ * rows the batch appended, and compacts the rows it keeps in their order; only
+ * those become pending (hsg_stats.pending_rows, hsg_pending_rows, hsg_drain),
+ * with src_index unchanged -- a dropped record's row is simply absent.
+ *
+ * HSG_W_COL arg names aggregate `arg` of the op (cfg->aggs[arg]); its type is
+ * static: HSG_COUNT_ALL and HSG_COUNT are i64, HSG_SUM / HSG_MIN / HSG_MAX /
+ * HSG_LAST have their column's type, HSG_AVG is f64. The program reads the
+ * 8-byte word the row carries, the reference's initial values included
+ * (maxBound / minBound of a MIN / MAX nothing reached, 0 of a LAST): they are
+ * Numbers and compare as such; literal forms are not looked at. Every alias
+ * is in the object, so COL is never the error value -- with one exception the
+ * engine defines, HSG_AVG not being in the reference: an f64 output that is
+ * NaN (HSG_AVG with COUNT(col) = 0, see hsg_agg_kind) is the error value, and
+ * the row is dropped unless an OR / AND / BETWEEN rule decides before it.
+ * Everything else is the WHERE semantics above, unchanged. A row is kept only
+ * when the result is true.
+ *
+ * HAVING filters the emitted rows only: the state, hsg_dump_state,
+ * hsg_view_get, watermarks and the pairs / touched / late_dropped statistics
+ * are those of the op without it (the reference's materialized store sits
+ * before the filter). The reference ignores HAVING on a windowed GROUP BY
+ * (Codegen.hs:554-559); this ABI is wider: any window kind with
+ * HSG_EMIT_PER_RECORD or HSG_EMIT_PER_BATCH. The rows are written, then
+ * compacted: the changelog room check ahead of a push (HSG_E_CAPACITY) stays
+ * the batch's worst case before the filter. */
 
 typedef struct hsg_engine hsg_engine;
 typedef struct hsg_op hsg_op;
@@ -316,6 +347,9 @@ typedef struct {
   uint64_t where_dropped;     /* records of the last batch (this rank's ingest) that arrived
                                  keyed and were masked by the op's WHERE program          */
   uint64_t where_dropped_total;
+  uint64_t having_dropped;    /* changelog rows of the last batch (this rank's) that the op's
+                                 HAVING program removed before they became pending        */
+  uint64_t having_dropped_total;
 } hsg_stats;
 
 /* Completion callback of hsg_push_batch_async: rc is what hsg_push_batch
@@ -351,6 +385,21 @@ int  hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_ty
  * sharded engine, like hsg_op_create. */
 int  hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *prog, int32_t n,
                          hsg_op **out);
+/* Type-check a HAVING program against the op's aggregate outputs; pure host
+ * code (no GPU). As hsg_where_check, with every column in [0, cfg->n_aggs)
+ * and typed as above; the messages begin "having: ". */
+int  hsg_having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg, char *err, size_t err_len);
+/* hsg_op_create with a WHERE program (n_where == 0: none) and a HAVING program
+ * (n_having == 0: none); with both 0 it is hsg_op_create, with n_having == 0
+ * hsg_op_create_where. The programs are copied and fixed for the op's life;
+ * hsg_op_reset keeps them. HSG_E_INVALID (message in hsg_engine_last_error)
+ * for a program its check refuses, and for a HAVING program on an
+ * HSG_EMIT_NONE op, which has nothing to filter. Collective on a sharded
+ * engine, like hsg_op_create; the filter itself is local to each rank's rows. */
+int  hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n_where,
+                            const hsg_where_ins *having, int32_t n_having, hsg_op **out);
+/* Rows of one compaction tile of the HAVING pass (tests size their segments by it). */
+int  hsg_having_tile_rows(void);
 void hsg_op_destroy(hsg_op *op);
 int  hsg_op_reset(hsg_op *op);            /* drop all state and pending rows          */
 const char *hsg_last_error(const hsg_op *op);

@@ -208,6 +208,18 @@ class hsg_rows(C.Structure):
     ]
 
 
+class hsg_probe(C.Structure):
+    """The stream side of hsg_table_join: one poll batch's keys, arrival order."""
+
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("mem", C.c_int32),
+        ("reserved", C.c_int32),
+        ("key_id", C.c_void_p),
+        ("ready_event", C.c_void_p),
+    ]
+
+
 class hsg_stats(C.Structure):
     _fields_ = [
         ("batches", C.c_uint64),
@@ -270,6 +282,8 @@ EXPORTED_SYMBOLS = [
     "hsg_state_rows",
     "hsg_dump_state",
     "hsg_view_get",
+    "hsg_table_join",
+    "hsg_table_join_tile",
     "hsg_op_stats",
     "hsg_testing_set_knob",
 ]

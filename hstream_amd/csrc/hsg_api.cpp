@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "hsg_internal.h"
+#include "hsg_kernels.h"
 #include "hsg_ops.h"
 #include "hsg_where.h"
 
@@ -972,6 +973,34 @@ extern "C" int hsg_view_get(hsg_op *op, const uint32_t *key_ids, uint32_t n_keys
     return HSG_E_DEVICE;
   }
 }
+
+extern "C" int hsg_table_join(hsg_op *table, const hsg_probe *probe, hsg_rows *out, uint64_t *n_out) {
+  try {
+    hsg_op *op = table;
+    if (!op || !n_out) return HSG_E_INVALID;
+    wait_idle(op);
+    if (!probe) return fail(op->err, HSG_E_INVALID, "table_join: null probe");
+    int rc = check_rows(op, out);
+    if (rc != HSG_OK) return rc;
+    *n_out = 0;
+    // joinTableProcessor reads a KV store (getKVStateStore); window and session stores are none
+    if (op->cfg.window_kind != HSG_UNWINDOWED)
+      return fail(op->err, HSG_E_INVALID, "table_join: the table must be an unwindowed op");
+    if (probe->reserved != 0) return fail(op->err, HSG_E_INVALID, "table_join: probe.reserved must be 0");
+    if (probe->mem != HSG_MEM_HOST && probe->mem != HSG_MEM_DEVICE)
+      return fail(op->err, HSG_E_INVALID, "table_join: bad probe mem");
+    if (probe->n > op->eng->batch_cap)
+      return fail(op->err, HSG_E_INVALID, "table_join: probe larger than the engine's batch_capacity");
+    if (probe->n && !probe->key_id) return fail(op->err, HSG_E_INVALID, "table_join: null key_id");
+    if (probe->n == 0) return HSG_OK;
+    HIP_TRY(op, hipSetDevice(op->eng->device));
+    return op_table_join(op->dev, op->cfg, op->prog, probe, out, n_out, op->err);
+  } catch (...) {
+    return HSG_E_DEVICE;
+  }
+}
+
+extern "C" int hsg_table_join_tile(void) { return (int)hsg::kTjTile; }
 
 extern "C" int hsg_op_stats(const hsg_op *op, hsg_stats *out) {
   if (!op || !out) return HSG_E_INVALID;

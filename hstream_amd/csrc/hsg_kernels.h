@@ -74,6 +74,20 @@ void launch_view_kv_rows(hipStream_t s, const TwTable &t, const Program &prog, c
 void launch_view_ss_rows(hipStream_t s, const SessTable &t, const Program &prog, const uint32_t *keys, uint32_t nk,
                          const int64_t *slot, const uint64_t *off, OutCols out, uint64_t out_cap);
 
+// stream-table join (hsg_table_join: op_device.cpp op_table_join / k_tjoin.hip).
+// The probe batch's keys (device memory, arrival order, HSG_KEY_NONE allowed)
+// are cut into tiles of kTjTile records, one workgroup each.
+constexpr uint64_t kTjTile = 1024;
+inline uint64_t tjoin_tiles(uint64_t n) { return (n + kTjTile - 1) / kTjTile; }
+// each record's table slot (-1: no live row) -> slot[n]; the tiles' hit counts
+// -> es.cnt, their exclusive scan -> es.off, the total -> *total (device)
+void launch_tjoin_find(hipStream_t s, const TwTable &t, const uint32_t *keys, uint64_t n, int64_t *slot,
+                       const EmitScratch &es, uint64_t *total);
+// the hits' rows, rendered, in arrival order at out[0 .. total); null columns
+// of out are skipped
+void launch_tjoin_rows(hipStream_t s, const TwTable &t, const Program &prog, const uint32_t *keys, uint64_t n,
+                       const int64_t *slot, const EmitScratch &es, OutCols out, uint64_t out_cap);
+
 // multi-GPU key exchange (exchange.cpp / k_exchange.hip)
 int exchange_device_init(OpDevice &d, const hsg_op_config &cfg, uint64_t batch_cap, std::string &err);
 void exchange_device_free(OpDevice &d);

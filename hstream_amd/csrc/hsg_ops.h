@@ -192,6 +192,16 @@ struct OpDevice {
   bool pr_part = false;
   void *scratch = nullptr;
   uint64_t scratch_bytes = 0;
+  // stream-table join scratch (op_table_join): slot words, tile counts and
+  // offsets, staged host keys in one allocation, and the temporary rows of a
+  // host-memory answer; both grow to the largest probe seen and are kept, so
+  // a steady stream of equal-sized probes allocates nothing
+  struct TjoinScratch {
+    void *mem = nullptr;
+    uint64_t cap = 0;      // records mem is carved for
+    OutCols tmp = {};
+    uint64_t tmp_cap = 0;  // rows
+  } tj;
   // exchange buffers (multi-GPU)
   void *xsend = nullptr;
   void *xrecv = nullptr;
@@ -270,5 +280,9 @@ int op_dump(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const hs
 // HSG_KEY_NONE, nk <= HSG_VIEW_MAX_KEYS; host memory) in the dump's order
 int op_view_get(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const uint32_t *keys, uint32_t nk,
                 const hsg_rows *out, uint64_t *n_out, std::string &err);
+// hsg_table_join on an unwindowed op: one row per record of the probe batch
+// (validated by the caller, n > 0) whose key has a live row, in arrival order
+int op_table_join(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const hsg_probe *probe,
+                  const hsg_rows *out, uint64_t *n_out, std::string &err);
 
 }  // namespace hsg

@@ -138,18 +138,27 @@ __device__ inline int64_t tw_claim_exclusive(const TwTable &t, uint64_t g, uint3
   return tw_ovf_claim(t, g, fresh);
 }
 
-// Lookup only (after the aggregation pass has inserted every group).
-__device__ inline int64_t tw_find(const TwTable &t, uint64_t g) {
-  const uint64_t base = tw_region_base(t, g);
-  uint64_t s = tw_home_in(t, g);
+// Lookup only (after the aggregation pass has inserted every group), in two
+// steps, so that a caller with several groups to find (k_tjoin.hip) can issue
+// the home-slot loads of all of them before it looks at any: tw_home is the
+// group's home slot, tw_find_from the probe from there, given the key word
+// `cur` the caller loaded from it.
+__device__ inline uint64_t tw_home(const TwTable &t, uint64_t g) { return tw_region_base(t, g) + tw_home_in(t, g); }
+__device__ inline int64_t tw_find_from(const TwTable &t, uint64_t g, uint64_t home, uint64_t cur) {
+  const uint64_t base = home & ~t.rmask;
+  uint64_t s = home & t.rmask;
   const uint64_t step = tw_step(t), n = (t.rmask + 1) / step;
   for (uint64_t probe = 0; probe < n && probe < kMaxProbes; ++probe) {
-    uint64_t cur = *t.key(base + s);
     if (cur == g) return (int64_t)(base + s);
     if (cur == kEmpty) return -1;
     s = (s + step) & t.rmask;
+    cur = *t.key(base + s);
   }
   return tw_ovf_find(t, g);  // the probe met no free slot
+}
+__device__ inline int64_t tw_find(const TwTable &t, uint64_t g) {
+  const uint64_t home = tw_home(t, g);
+  return tw_find_from(t, g, home, *t.key(home));
 }
 
 }  // namespace hsg

@@ -428,6 +428,11 @@ void op_device_free(OpDevice &d) {
   if (d.hv_state) hipFree(d.hv_state);
   d.hv_state = nullptr;
   d.hv_state_words = 0;
+  if (d.tj.mem) hipFree(d.tj.mem);
+  d.tj.mem = nullptr;
+  d.tj.cap = 0;
+  free_out(d.tj.tmp);
+  d.tj.tmp_cap = 0;
   if (d.xsend) hipFree(d.xsend);
   if (d.xrecv) hipFree(d.xrecv);
   d.xsend = d.xrecv = nullptr;
@@ -1515,6 +1520,89 @@ int op_view_get(OpDevice &d, const hsg_op_config &cfg, const Program &prog, cons
                   : sort_dump_rows(d, out, total, cfg.n_aggs, err);
   }
   return rc;
+}
+
+// hsg_table_join: the table's row for each record of a poll batch, in arrival
+// order (k_tjoin.hip). Find pass, the total to the host (nothing is written
+// when the rows do not fit out->capacity: *n_out = the rows needed,
+// HSG_E_CAPACITY), then the rows pass: straight into the caller's columns when
+// they are device memory, else into the op's temporary and from there to the
+// host. Reads only, like op_view_get, whose preamble this is. The scratch is
+// the op's (OpDevice::tj), grown on demand and kept.
+int op_table_join(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const hsg_probe *probe,
+                  const hsg_rows *out, uint64_t *n_out, std::string &err) {
+  *n_out = 0;
+  wait_table_reset(d);
+  int rc = fetch_scalars(d, err);
+  if (rc != HSG_OK) return rc;
+  const uint64_t n = probe->n, tiles = tjoin_tiles(n);
+  if (n > d.tj.cap) {
+    if (d.tj.mem) DTRY(hipFree(d.tj.mem));
+    d.tj.mem = nullptr;
+    d.tj.cap = 0;
+    // [slot | off | partial | total] (8 B), [cnt | keys] (4 B)
+    DTRY(hipMalloc(&d.tj.mem, (n + tiles + scan_partials_needed(tiles) + 8 + 1) * 8 + (tiles + n) * 4));
+    d.tj.cap = n;
+  }
+  if (!d.h_tmp) DTRY(hipHostMalloc((void **)&d.h_tmp, 8 * sizeof(uint64_t), hipHostMallocDefault));
+  // carved for the capacity, so the addresses do not move between equal calls
+  const uint64_t ctiles = tjoin_tiles(d.tj.cap);
+  int64_t *d_slot = (int64_t *)d.tj.mem;
+  EmitScratch es;
+  es.off = (uint64_t *)(d_slot + d.tj.cap);
+  es.partial = es.off + ctiles;
+  uint64_t *d_total = es.partial + scan_partials_needed(ctiles) + 8;
+  es.cnt = (uint32_t *)(d_total + 1);
+  uint32_t *d_keys = es.cnt + ctiles;
+  const uint32_t *keys = probe->key_id;
+  if (probe->mem == HSG_MEM_DEVICE) {
+    // the producer's stream is not ordered with ours: wait on its event
+    if (probe->ready_event) DTRY(hipStreamWaitEvent(d.stream, (hipEvent_t)probe->ready_event, 0));
+  } else {
+    DTRY(hipMemcpyAsync(d_keys, probe->key_id, n * 4, hipMemcpyHostToDevice, d.stream));
+    keys = d_keys;
+  }
+  launch_tjoin_find(d.stream, d.tw, keys, n, d_slot, es, d_total);
+  DTRY(hipGetLastError());
+  DTRY(hipMemcpyAsync(d.h_tmp, d_total, 8, hipMemcpyDeviceToHost, d.stream));
+  DTRY(hipStreamSynchronize(d.stream));
+  const uint64_t total = d.h_tmp[0];
+  *n_out = total;
+  if (total > out->capacity) {
+    err = "table_join: rows capacity < the matching records";
+    return HSG_E_CAPACITY;
+  }
+  if (total == 0) return HSG_OK;
+
+  if (out->mem == HSG_MEM_DEVICE) {
+    OutCols o;
+    memset(&o, 0, sizeof(o));
+    o.key = out->key_id;
+    o.ws = out->win_start;
+    o.we = out->win_end;
+    o.src = out->src_index;
+    for (int j = 0; j < cfg.n_aggs && out->aggs; ++j) o.agg[j] = (int64_t *)out->aggs[j];
+    o.form = out->form;  // (an op without literal forms renders 0)
+    launch_tjoin_rows(d.stream, d.tw, prog, keys, n, d_slot, es, o, total);
+    DTRY(hipGetLastError());
+    DTRY(hipStreamSynchronize(d.stream));
+    return HSG_OK;
+  }
+  if (total > d.tj.tmp_cap) {
+    // a probe of n records has at most n matches: sized by the probe, so the
+    // hit rate of the next equal-sized one does not matter
+    free_out(d.tj.tmp);
+    d.tj.tmp_cap = 0;
+    rc = alloc_out(d.tj.tmp, n, cfg.n_aggs, err, d.forms);
+    if (rc != HSG_OK) {
+      free_out(d.tj.tmp);
+      return rc;
+    }
+    d.tj.tmp_cap = n;
+  }
+  launch_tjoin_rows(d.stream, d.tw, prog, keys, n, d_slot, es, d.tj.tmp, total);
+  DTRY(hipGetLastError());
+  return op_copy_rows(d, d.tj.tmp, 0, total, cfg.n_aggs, out, err);  // (synchronises the stream)
 }
 
 }  // namespace hsg

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import abi
-from .columnar import OpHandle, OpSpec, Rows, alloc_rows, declare_op_functions, truncate
+from .columnar import OpHandle, OpSpec, Rows, _is_torch, alloc_rows, declare_op_functions, truncate
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhstream_gpu.so")
 # diagnostics only: HSG_LIB_PATH names another build of the same library
@@ -62,6 +62,10 @@ def load_library(path=LIB_PATH):
     L.hsg_op_wait.restype = C.c_int
     L.hsg_view_get.argtypes = [vp, vp, C.c_uint32, P(abi.hsg_rows), P(C.c_uint64)]
     L.hsg_view_get.restype = C.c_int
+    L.hsg_table_join.argtypes = [vp, P(abi.hsg_probe), P(abi.hsg_rows), P(C.c_uint64)]
+    L.hsg_table_join.restype = C.c_int
+    L.hsg_table_join_tile.argtypes = []
+    L.hsg_table_join_tile.restype = C.c_int
     L.hsg_testing_set_knob.argtypes = [C.c_int32, C.c_int64]
     L.hsg_testing_set_knob.restype = C.c_int
     declare_op_functions(L, "hsg")
@@ -114,6 +118,27 @@ def having_check(program, spec: OpSpec):
 def having_tile_rows() -> int:
     """Rows of one compaction tile of the HAVING pass (hsg_having_tile_rows)."""
     return load_library().hsg_having_tile_rows()
+
+
+def table_join_tile() -> int:
+    """Records per compaction tile of the stream-table join (hsg_table_join_tile)."""
+    return load_library().hsg_table_join_tile()
+
+
+def make_probe(key_ids, mem=None, ready_event=None):
+    """An hsg_probe over a numpy array (host) or a torch tensor (device) of
+    key ids in arrival order. Returns (hsg_probe, keepalive)."""
+    if _is_torch(key_ids):
+        keys = key_ids.contiguous()
+        if mem is None:
+            mem = abi.HSG_MEM_DEVICE if keys.is_cuda else abi.HSG_MEM_HOST
+        n, ptr = int(keys.numel()), keys.data_ptr()
+    else:
+        keys = np.ascontiguousarray(np.asarray(key_ids, dtype=np.uint32).ravel())
+        if mem is None:
+            mem = abi.HSG_MEM_HOST
+        n, ptr = int(keys.size), keys.ctypes.data
+    return abi.hsg_probe(n=n, mem=mem, reserved=0, key_id=ptr if n else None, ready_event=ready_event), keys
 
 
 def comm_unique_id() -> bytes:
@@ -254,6 +279,37 @@ class GpuOp(OpHandle):
                 continue
             self._check(rc, "view_get")
             return truncate(arrs, got.value)
+
+    def table_join_into(self, key_ids, rows, mem=None, ready_event=None):
+        """hsg_table_join into caller-owned columns (an abi.hsg_rows, host or
+        device memory): (status, rows written or needed). HSG_E_CAPACITY is
+        returned, not raised; any other failure raises."""
+        probe, keep = make_probe(key_ids, mem, ready_event)
+        got = C.c_uint64(0)
+        rc = self._lib.hsg_table_join(self._h, C.byref(probe), C.byref(rows), C.byref(got))
+        del keep
+        if rc != abi.HSG_E_CAPACITY:
+            self._check(rc, "table_join")
+        return rc, got.value
+
+    def table_join(self, key_ids, capacity=None, mem=None) -> Rows:
+        """hsg_table_join: this unwindowed op as the table of a stream-table
+        join. key_ids are the stream records' keys in this op's dictionary, in
+        arrival order (numpy, or a torch device tensor as push accepts);
+        HSG_KEY_NONE matches nothing. One row per record whose key has a live
+        row, in arrival order, src_index = the record's index. The rows land in
+        host columns of `capacity` rows (default: one per record); when they do
+        not fit, the call is made once more with the count it reported."""
+        n = int(key_ids.numel()) if _is_torch(key_ids) else int(np.asarray(key_ids).size)
+        cap = int(capacity) if capacity is not None else max(1, n)
+        for attempt in (0, 1):
+            rows, arrs, keep = alloc_rows(cap, self._f64, self._forms)
+            rc, got = self.table_join_into(key_ids, rows, mem)
+            if rc == abi.HSG_E_CAPACITY and attempt == 0:
+                cap = got
+                continue
+            self._check(rc, "table_join")
+            return truncate(arrs, got)
 
     def stats(self) -> dict:
         s = abi.hsg_stats()

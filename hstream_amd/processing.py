@@ -450,6 +450,60 @@ def select_view_result(rows, windowed: bool, session: bool, size_ms: int, names:
     return {f"winStart = {starts[i]} ,winEnd = {starts[i] + int(size_ms)}": vals[i] for i in order}
 
 
+# ---------------------------------------------------------------------------
+# tables as join sides (Stream.table, Stream.joinTable)
+# ---------------------------------------------------------------------------
+def table(engine, key_field: str, fields: Sequence, materialized: Materialized) -> Table:
+    """Stream.table / tableStoreProcessor (Stream.hs:79-129): a stream read as a
+    table, the latest value per key, kept in HBM to be joined against
+    (joinTable). `fields` names the value's fields to keep, each a name or a
+    (name, is_float) pair. It is an unwindowed HSG_EMIT_NONE op with one LAST
+    per field; feed it with Table.process.
+
+    One difference: the reference replaces the whole stored object per record
+    (ksPut keyBytes valueBytes), whereas LAST per field keeps each field's last
+    PRESENT value, so a record that lacks a field leaves that field's earlier
+    value in place where the reference would drop it. The two are equal when
+    every record carries every field."""
+    aggs = []
+    for f in fields:
+        name, is_float = (f, False) if isinstance(f, str) else (f[0], bool(f[1]))
+        aggs.append(LAST(name, name, is_float))
+    return GroupedStream(engine, key_field).aggregate(aggs, materialized, emit=abi.HSG_EMIT_NONE)
+
+
+def join_table_result(records, rows: Rows, aliases: Sequence[str], joiner, key_field: str = "key"):
+    """The records joinTableProcessor forwards (Stream.hs:334-344) for one poll
+    batch `records` of the stream side, given the table's answer `rows`
+    (hsg_table_join: one row per matching record, src_index = its index in the
+    batch): for each row in src_index order, the stream record with its value
+    replaced by joiner(stream value, {alias: table value}); key and timestamp
+    are the stream record's. Pure: no GPU."""
+    out = []
+    for i in np.argsort(np.asarray(rows.src_index), kind="stable"):
+        rec = records[int(rows.src_index[i])]
+        v2 = {a: rows.aggs[j][i].item() for j, a in enumerate(aliases)}
+        out.append({"key": rec["value"][key_field], "value": joiner(rec["value"], v2), "timestamp": rec["timestamp"]})
+    return out
+
+
+def joinTable(table: Table, joiner, records) -> list:
+    """Stream.joinTable (Stream.hs:302-344) for one poll batch of the stream
+    side: each record whose key has a row in `table` (an unwindowed Table, the
+    KV store joinTableProcessor reads) is forwarded with joiner(value, row),
+    in arrival order; the others are dropped. The keys are looked up in the
+    table's dictionary without being inserted (KeyDict.find): a record without
+    the key field, or with a key the table has never seen, probes as
+    HSG_KEY_NONE and matches nothing. The lookups run on the GPU
+    (GpuOp.table_join)."""
+    kf = table.grouped.key_field
+    find = table.mat.keys.find
+    kids = np.fromiter((find(r["value"][kf]) if kf in r["value"] else abi.HSG_KEY_NONE for r in records),
+                       dtype=np.uint32, count=len(records))
+    rows = table.op.table_join(kids)
+    return join_table_result(records, rows, [a.name for a in table.aggs], joiner, kf)
+
+
 def runTask(poll, table: Table, max_polls=None, sink=None):
     """Processor.hs:99-144 for one windowed aggregate: poll a batch, advance the
     task's stream time over every polled record, run the operator, forward

@@ -31,6 +31,9 @@
  *       ksGet / findSessions / ssGet (Store.hs:59,243-272) and with them the one
  *       read of a view, SELECT ... FROM view WHERE key = x (SelectViewPlan,
  *       hstream/src/HStream/Server/Handler.hs:277-323), by key instead of from a dump.
+ *   hsg_table_join
+ *       Stream.joinTable / joinTableProcessor (.../Processing/Stream.hs:302-344): the
+ *       ksGet per stream record, for a whole poll batch, against an unwindowed op.
  *   hsg_agg kinds
  *       the SQL aggregate components of hstream-sql/src/HStream/SQL/Codegen.hs:399-469
  *       (COUNT(*), COUNT(col), SUM, MIN, MAX, non-aggregate passthrough = HSG_LAST)
@@ -469,6 +472,50 @@ int  hsg_dump_state(hsg_op *op, hsg_rows *out, uint64_t *n_out);
  * the caller unites the ranks' answers. */
 #define HSG_VIEW_MAX_KEYS 1024
 int  hsg_view_get(hsg_op *op, const uint32_t *key_ids, uint32_t n_keys, hsg_rows *out, uint64_t *n_out);
+
+/* Stream-table join: the keys of one poll batch of the stream side, probed
+ * against the state of an HSG_UNWINDOWED op, the Table that
+ * GroupedStream.aggregate returns (GroupedStream.hs:53-56). This is the
+ * reference's Stream.joinTable (hstream-processing/src/HStream/Processing/
+ * Stream.hs:302-344): joinTableProcessor does ksGet key tableStore per stream
+ * record, forwards joiner recordValue v2 on a hit and nothing on a miss. */
+typedef struct {
+  uint64_t n;              /* stream records of this poll batch, arrival order        */
+  int32_t  mem;            /* hsg_mem of key_id                                       */
+  int32_t  reserved;       /* 0                                                       */
+  const uint32_t *key_id;  /* the stream's key in the TABLE op's dictionary;
+                              HSG_KEY_NONE = no key, matches nothing                  */
+  void *ready_event;       /* as hsg_batch.ready_event (device keys)                  */
+} hsg_probe;
+
+/* One output row per probe record whose key has a live row in `table`, in
+ * arrival order: key_id is the record's key, win_start = win_end = 0,
+ * src_index the record's index in the probe batch (0 .. n-1; the caller's
+ * joiner pairs the stream record with the row through it), aggs[j] and form
+ * what hsg_view_get returns for that key. out may be host or device memory;
+ * device columns are written in place. Duplicate keys each get their own row;
+ * HSG_KEY_NONE, ids never pushed and keys another rank owns match nothing.
+ * Cost follows the probe batch (one table row read per record), not the
+ * state's size.
+ *
+ * Only HSG_UNWINDOWED ops are tables (joinTableProcessor calls
+ * getKVStateStore; window and session stores are not KV stores): any other
+ * window kind gives HSG_E_INVALID. So do a NULL table, probe or n_out, a NULL
+ * key_id with n > 0, n above the engine's batch_capacity, and reserved != 0.
+ * n == 0 gives HSG_OK with 0 rows. Same capacity rule as hsg_drain: if the
+ * matches do not fit out->capacity, nothing is written, *n_out is the number
+ * needed (counted before any row is written, so a retry with that capacity
+ * succeeds) and the call returns HSG_E_CAPACITY.
+ *
+ * The call reads only: state, pending changelog rows, registered changelog
+ * columns, hsg_stats and the watermark are untouched (the reference's join
+ * processor has no stream-time effect). Like every call on an op it first
+ * waits for the op's queued asynchronous pushes, and it is serialised with
+ * the op's other calls by the caller. On a sharded engine it is NOT
+ * collective: a rank answers for the keys it owns. */
+int  hsg_table_join(hsg_op *table, const hsg_probe *probe, hsg_rows *out, uint64_t *n_out);
+/* Records per compaction tile of the join's kernels (tests size their shapes by it). */
+int  hsg_table_join_tile(void);
 
 /* Counters are cumulative since hsg_op_create (hsg_op_reset keeps them);
  * "last batch" fields describe the most recent hsg_push_batch. */

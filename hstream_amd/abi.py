@@ -3,6 +3,7 @@
 Kept in one place so the product binding (``hstream_amd.engine``) and the test
 oracle binding (``oracle/pyoracle.py``) describe the exact same ABI.
 """
+import collections
 import ctypes as C
 
 HSG_OK = 0
@@ -124,6 +125,66 @@ def where_array(program):
     """A program -- hsg_where_ins, or (op,) / (op, arg) tuples -- as a C array."""
     items = [p if isinstance(p, hsg_where_ins) else where_ins(*p) for p in program]
     return (hsg_where_ins * max(1, len(items)))(*items), len(items)
+
+
+# computed columns (hsg_op_create_mapped): value programs over the batch's columns
+HSG_MAP_STRICT = 1
+HSG_MAP_MAX_EXPRS = 8
+HSG_MAP_MAX_INS = 64
+
+
+class hsg_map_expr(C.Structure):
+    _fields_ = [("prog", C.POINTER(hsg_where_ins)), ("n", C.c_int32), ("flags", C.c_uint32)]
+
+
+class hsg_map_stats(C.Structure):
+    _fields_ = [
+        ("map_dropped", C.c_uint64),
+        ("map_dropped_total", C.c_uint64),
+        ("computed_cols", C.c_uint32),
+        ("aliased_cols", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class MapExpr(collections.namedtuple("MapExpr", "prog flags")):
+    """One expression of a map: its value program -- hsg_where_ins, or (op,) /
+    (op, arg) tuples -- and its flags (HSG_MAP_STRICT)."""
+
+    __slots__ = ()
+
+    def __new__(cls, prog, flags=0):
+        return super().__new__(cls, list(prog), int(flags))
+
+
+def _map_expr(e):
+    """A map entry as a MapExpr: one already, or a bare program (flags 0)."""
+    return e if isinstance(e, MapExpr) else MapExpr(e)
+
+
+def map_expr_type(e, col_types):
+    """The static type of a map expression: HSG_F64 iff an f64 column or
+    constant takes part (include/hstream_gpu.h)."""
+    prog, _ = _map_expr(e)
+    for p in prog:
+        op, arg = (p.op, p.arg) if isinstance(p, hsg_where_ins) else (p[0], p[1] if len(p) > 1 else 0)
+        if op == HSG_W_F64 or (op == HSG_W_COL and 0 <= arg < len(col_types) and col_types[arg] == HSG_F64):
+            return HSG_F64
+    return HSG_I64
+
+
+def map_array(exprs):
+    """A map -- a list of MapExpr, or of bare programs (flags 0) -- as a C
+    array of hsg_map_expr. Returns (array, n_exprs, keepalive)."""
+    keep, items = [], []
+    for e in exprs:
+        prog, flags = _map_expr(e)
+        arr, n = where_array(prog)
+        keep.append(arr)
+        items.append(hsg_map_expr(prog=C.cast(arr, C.POINTER(hsg_where_ins)), n=n, flags=int(flags)))
+    return (hsg_map_expr * max(1, len(items)))(*items), len(items), keep
 
 
 class hsg_engine_config(C.Structure):
@@ -270,6 +331,10 @@ EXPORTED_SYMBOLS = [
     "hsg_having_check",
     "hsg_op_create_filtered",
     "hsg_having_tile_rows",
+    "hsg_map_check",
+    "hsg_op_create_mapped",
+    "hsg_op_map_stats",
+    "hsg_map_grid_threads",
     "hsg_op_destroy",
     "hsg_op_reset",
     "hsg_last_error",

@@ -37,15 +37,29 @@ class OpSpec:
     # (HSG_W_COL j = aggs[j]): the op filters and compacts the changelog rows
     # each push appends (hsg_op_create_filtered); None = no filter.
     having: Optional[Sequence] = None
+    # Computed columns (hsg_op_create_mapped): value programs over the batch's
+    # columns, each an abi.MapExpr(program, flags) (flags: abi.HSG_MAP_STRICT)
+    # or a bare program.
+    # aggs[].column then indexes these expressions, col_types stays the batch.
+    map: Optional[Sequence] = None
 
     @property
     def literal_forms(self) -> bool:
         return bool(self.flags & abi.HSG_OPF_LITERAL_FORMS)
 
+    def agg_col_types(self) -> List[int]:
+        """The types of the columns the aggregates index: the map's
+        expressions (static: f64 iff an f64 column or constant takes part),
+        or the batch's columns."""
+        if not self.map:
+            return list(self.col_types)
+        return [abi.map_expr_type(e, self.col_types) for e in self.map]
+
     def agg_is_f64(self) -> List[bool]:
         out = []
+        col_types = self.agg_col_types()
         for kind, col in self.aggs:
-            ct = self.col_types[col] if kind not in (abi.HSG_COUNT_ALL,) and 0 <= col < len(self.col_types) else abi.HSG_I64
+            ct = col_types[col] if kind not in (abi.HSG_COUNT_ALL,) and 0 <= col < len(col_types) else abi.HSG_I64
             out.append(abi.agg_output_is_f64(kind, ct))
         return out
 

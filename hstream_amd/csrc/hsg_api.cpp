@@ -175,7 +175,7 @@ int build_program(const hsg_op_config &cfg, const std::vector<int32_t> &col_type
 // ---------------------------------------------------------------------------
 // WHERE / HAVING program (include/hstream_gpu.h hsg_where_ins): host type check
 // ---------------------------------------------------------------------------
-static int validate_config(const hsg_op_config *c, std::string &err);
+static int validate_config(const hsg_op_config *c, std::string &err, int32_t agg_cols = -1);
 
 namespace hsg {
 
@@ -274,7 +274,128 @@ void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_type
   }
 }
 
+// ---- computed columns: the map's value programs ------------------------------
+int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, int32_t *out_types,
+              std::string &err) {
+  if (!exprs) return fail(err, HSG_E_INVALID, "map: null expressions");
+  if (n_exprs < 1 || n_exprs > HSG_MAP_MAX_EXPRS)
+    return fail(err, HSG_E_INVALID, "map: " + std::to_string(n_exprs) + " expressions outside 1.." +
+                                        std::to_string(HSG_MAP_MAX_EXPRS));
+  if (n_cols < 0 || n_cols > kMaxCols || (n_cols > 0 && !col_types))
+    return fail(err, HSG_E_INVALID, "map: bad value columns (max " + std::to_string(kMaxCols) + ")");
+  int64_t total = 0;
+  for (int j = 0; j < n_exprs; ++j) {
+    const std::string what = "map: expr " + std::to_string(j) + ": ";
+    const hsg_map_expr &x = exprs[j];
+    if (!x.prog) return fail(err, HSG_E_INVALID, what + "null program");
+    if (x.n < 1 || x.n > HSG_MAP_MAX_INS)
+      return fail(err, HSG_E_INVALID, what + "program length " + std::to_string(x.n) + " outside 1.." +
+                                          std::to_string(HSG_MAP_MAX_INS));
+    if (x.flags & ~HSG_MAP_STRICT) return fail(err, HSG_E_INVALID, what + "bad flags");
+    total += x.n;
+    if (total > HSG_MAP_MAX_INS)
+      return fail(err, HSG_E_INVALID, what + std::to_string(total) + " instructions with the expressions before it, more than " +
+                                          std::to_string(HSG_MAP_MAX_INS));
+    bool is_f64[HSG_WHERE_MAX_DEPTH];  // a value's static type, as the device carries it (hsg_pred.h)
+    int depth = 0;
+    for (int pc = 0; pc < x.n; ++pc) {
+      const hsg_where_ins &in = x.prog[pc];
+      const std::string at = what + "instruction " + std::to_string(pc) + ": ";
+      int pops = 0;
+      bool f64 = false;
+      switch (in.op) {
+        case HSG_W_COL:
+          if (in.arg < 0 || in.arg >= n_cols)
+            return fail(err, HSG_E_INVALID, at + "column " + std::to_string(in.arg) + " out of range");
+          if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64)
+            return fail(err, HSG_E_INVALID, at + "bad column type");
+          f64 = col_types[in.arg] == HSG_F64;
+          break;
+        case HSG_W_I64: break;
+        case HSG_W_F64:
+          if (!(in.imm.f - in.imm.f == 0.0)) return fail(err, HSG_E_INVALID, at + "f64 constant is not finite");
+          f64 = true;
+          break;
+        case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
+        default:
+          return fail(err, HSG_E_INVALID, at + "opcode " + std::to_string(in.op) + " is not a value instruction");
+      }
+      if (depth < pops) return fail(err, HSG_E_INVALID, at + "stack underflow");
+      for (int k = 0; k < pops; ++k) f64 |= is_f64[depth - 1 - k];
+      depth -= pops;
+      if (depth >= HSG_WHERE_MAX_DEPTH)
+        return fail(err, HSG_E_INVALID, at + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
+      is_f64[depth++] = f64;
+    }
+    if (depth != 1)
+      return fail(err, HSG_E_INVALID, what + std::to_string(depth) + " values left on the stack, not one");
+    if (out_types) out_types[j] = is_f64[0] ? HSG_F64 : HSG_I64;
+  }
+  return HSG_OK;
+}
+
+void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, bool forms,
+                 const WhereProg &where, MapProg &out, MapPlan &plan) {
+  memset(&out, 0, sizeof(out));
+  plan = MapPlan();
+  out.where = where;
+  out.cols = where.n ? where.cols : 0;
+  out.forms = forms ? 1u : 0u;
+  for (int c = 0; c < n_cols; ++c)
+    if (col_types[c] == HSG_F64) out.f64 |= 1u << c;
+  plan.n_exprs = n_exprs;
+  plan.keys = where.n != 0;
+  for (int j = 0; j < n_exprs; ++j) {
+    const hsg_map_expr &x = exprs[j];
+    const bool strict = (x.flags & HSG_MAP_STRICT) != 0;
+    const bool alias = x.n == 1 && x.prog[0].op == HSG_W_COL;
+    plan.alias[j] = alias ? x.prog[0].arg : -1;
+    plan.ocol[j] = alias ? -1 : plan.n_out++;
+    plan.keys |= strict;
+    for (int pc = 0; pc < x.n; ++pc) {
+      const hsg_where_ins &in = x.prog[pc];
+      if (in.op == HSG_W_COL) plan.reads[j] |= 1u << in.arg;
+      if (in.op == HSG_W_F64 && in.imm.f != __builtin_trunc(in.imm.f)) plan.const_form[j] = true;
+    }
+    if (alias && !strict) continue;  // the caller's column as it is: nothing to run
+    for (int pc = 0; pc < x.n; ++pc) {
+      hsg_where_ins in = x.prog[pc];
+      // the literal-form bit of a constant: an F64 that is not integral (ops that keep forms only)
+      if (in.op == HSG_W_I64) in.arg = 0;
+      if (in.op == HSG_W_F64) in.arg = forms && in.imm.f != __builtin_trunc(in.imm.f) ? 1 : 0;
+      out.ins[out.n_ins++] = in;
+    }
+    out.cols |= plan.reads[j];
+    out.end[out.n_runs] = out.n_ins;
+    out.out[out.n_runs] = plan.ocol[j];
+    if (strict) out.strict |= 1u << out.n_runs;
+    ++out.n_runs;
+  }
+}
+
 }  // namespace hsg
+
+template <class F>
+static int checked_message(F check, char *err, size_t err_len) {
+  try {
+    std::string msg;
+    const int rc = check(msg);
+    if (err && err_len) {
+      const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
+      memcpy(err, msg.data(), k);
+      err[k] = 0;
+    }
+    return rc;
+  } catch (...) {
+    return HSG_E_OOM;
+  }
+}
+
+extern "C" int hsg_map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols,
+                             int32_t *out_types, char *err, size_t err_len) {
+  return checked_message(
+      [&](std::string &msg) { return map_check(exprs, n_exprs, col_types, n_cols, out_types, msg); }, err, err_len);
+}
 
 extern "C" int hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, char *err,
                                size_t err_len) {
@@ -440,6 +561,7 @@ struct hsg_op {
   uint32_t batch_id = 0;
   uint64_t rec_base = 0;
   hsg_stats stats;
+  hsg_map_stats map_stats = {};  // the map's counters (hsg_op_map_stats)
   // asynchronous pushes (hsg_push_batch_async): one completion thread per op
   std::mutex qmu;
   std::condition_variable qcv;
@@ -517,7 +639,8 @@ static void async_loop(hsg_op *op) {
   }
 }
 
-static int validate_config(const hsg_op_config *c, std::string &err) {
+// (agg_cols: what aggs[].column indexes, the map's expressions of a mapped op; -1: the batch's columns)
+static int validate_config(const hsg_op_config *c, std::string &err, int32_t agg_cols) {
   if (!c) return fail(err, HSG_E_INVALID, "null config");
   if (c->window_kind < HSG_TUMBLING || c->window_kind > HSG_UNWINDOWED) return fail(err, HSG_E_INVALID, "bad window_kind");
   if (c->emit_mode < HSG_EMIT_PER_RECORD || c->emit_mode > HSG_EMIT_NONE) return fail(err, HSG_E_INVALID, "bad emit_mode");
@@ -534,7 +657,7 @@ static int validate_config(const hsg_op_config *c, std::string &err) {
   for (int j = 0; j < c->n_aggs; ++j) {
     const hsg_agg &g = c->aggs[j];
     if (g.kind < HSG_COUNT_ALL || g.kind > HSG_LAST) return fail(err, HSG_E_INVALID, "bad aggregate kind");
-    if (g.kind != HSG_COUNT_ALL && (g.column < 0 || g.column >= c->n_cols))
+    if (g.kind != HSG_COUNT_ALL && (g.column < 0 || g.column >= (agg_cols >= 0 ? agg_cols : c->n_cols)))
       return fail(err, HSG_E_INVALID, "aggregate column out of range");
   }
   return HSG_OK;
@@ -545,20 +668,30 @@ uint64_t hsg_windows_per_record(const hsg_op_config &c) {
   return 1;
 }
 
-// hsg_op_create is the n == 0, n_having == 0 case.
-extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
-                                      const hsg_where_ins *having, int32_t n_having, hsg_op **out) {
+// hsg_op_create is the n_exprs == 0, n == 0, n_having == 0 case.
+extern "C" int hsg_op_create_mapped(hsg_engine *eng, const hsg_op_config *cfg, const hsg_map_expr *exprs, int32_t n_exprs,
+                                    const hsg_where_ins *where, int32_t n, const hsg_where_ins *having,
+                                    int32_t n_having, hsg_op **out) {
   try {
     if (!eng || !out) return HSG_E_INVALID;
     *out = nullptr;
-    int rc = validate_config(cfg, eng->err);
+    int rc = validate_config(cfg, eng->err, n_exprs != 0 ? n_exprs : -1);
     if (rc != HSG_OK) return rc;
     if (n != 0) {
       rc = where_check(where, n, cfg->col_types, cfg->n_cols, eng->err);
       if (rc != HSG_OK) return rc;
     }
+    // the aggregates' columns and their types: the map's expressions, or the batch's columns
+    int32_t mtypes[HSG_MAP_MAX_EXPRS];
+    hsg_op_config acfg = *cfg;
+    if (n_exprs != 0) {
+      rc = map_check(exprs, n_exprs, cfg->col_types, cfg->n_cols, mtypes, eng->err);
+      if (rc != HSG_OK) return rc;
+      acfg.n_cols = n_exprs;
+      acfg.col_types = mtypes;
+    }
     if (n_having != 0) {
-      rc = having_check(having, n_having, cfg, eng->err);
+      rc = having_check(having, n_having, &acfg, eng->err);
       if (rc != HSG_OK) return rc;
       if (cfg->emit_mode == HSG_EMIT_NONE)
         return fail(eng->err, HSG_E_INVALID, "having: an op that emits no rows (HSG_EMIT_NONE) has nothing to filter");
@@ -585,8 +718,8 @@ extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg,
     std::vector<hsg_agg> iaggs = op->aggs;
     op->user_cols = cfg->n_cols;
     for (int c = 0; c < cfg->n_cols; ++c) op->dev.col_map[c] = c;
-    if (n != 0) {
-      where_compile(where, n, cfg->col_types, cfg->n_cols, op->dev.where);
+    if (n != 0) where_compile(where, n, cfg->col_types, cfg->n_cols, op->dev.where);
+    if (n != 0 && n_exprs == 0) {
       int32_t to_internal[kMaxCols];
       int ni = 0;
       itypes.clear();
@@ -602,6 +735,17 @@ extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg,
         if (g.kind != HSG_COUNT_ALL) g.column = to_internal[g.column];
       op->cfg.n_cols = ni;
     }
+    if (n_exprs != 0) {
+      // internal column j is expression j: the batch's columns, the ones only
+      // the WHERE program reads included, are gone once the map ran (op_device.cpp
+      // stage_map). The pass runs the WHERE program itself (dev.where stays empty).
+      WhereProg wp = op->dev.where;
+      memset(&op->dev.where, 0, sizeof(op->dev.where));
+      map_compile(exprs, n_exprs, cfg->col_types, cfg->n_cols, forms, wp, op->dev.map_prog, op->dev.map);
+      itypes.assign(mtypes, mtypes + n_exprs);
+      iaggs = op->aggs;
+      op->cfg.n_cols = n_exprs;
+    }
     rc = build_program(op->cfg, itypes, iaggs, op->prog, eng->err, forms);
     if (rc != HSG_OK) { delete op; return rc; }
     op->dev.user_cols = cfg->n_cols;
@@ -609,7 +753,7 @@ extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg,
     if (n_having != 0) {
       // the changelog filter (k_having.hip): over the aggregate outputs, as the caller numbers them
       int32_t otypes[kMaxAggs];
-      having_types(cfg, otypes);
+      having_types(&acfg, otypes);
       where_compile(having, n_having, otypes, cfg->n_aggs, op->dev.having);
       op->dev.hv.n_aggs = cfg->n_aggs;
     }
@@ -658,6 +802,8 @@ extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg,
       delete op;
       return rc;
     }
+    op->map_stats.computed_cols = (uint32_t)op->dev.map.n_out;
+    op->map_stats.aliased_cols = (uint32_t)(op->dev.map.n_exprs - op->dev.map.n_out);
     op->stats.state_slots = (uint64_t)op->prog.n_slots;
     op->stats.state_row_bytes = 8ull * (uint64_t)op->prog.n_slots + (cfg->window_kind == HSG_SESSION ? 16ull : 8ull);
     op->stats.table_slots = op->dev.cap;
@@ -668,6 +814,11 @@ extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg,
   } catch (...) {
     return HSG_E_DEVICE;
   }
+}
+
+extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
+                                      const hsg_where_ins *having, int32_t n_having, hsg_op **out) {
+  return hsg_op_create_mapped(eng, cfg, nullptr, 0, where, n, having, n_having, out);
 }
 
 extern "C" int hsg_op_create_where(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
@@ -766,6 +917,16 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
       const uint64_t seen = op->dev.h_sc->scratch[kWhereWord];
       res.where_dropped = seen - op->dev.where_seen;
       op->dev.where_seen = seen;
+    }
+    if (op->dev.map.n_exprs) {
+      // the map pass keeps two cumulative 32-bit counts in the word: WHERE
+      // drops below, strict map drops above (k_map.hip)
+      const uint64_t seen = op->dev.h_sc->scratch[kWhereWord];
+      res.where_dropped = (uint32_t)((uint32_t)seen - (uint32_t)op->dev.where_seen);
+      op->dev.where_seen = (uint32_t)seen;
+      op->map_stats.map_dropped = (uint32_t)((uint32_t)(seen >> 32) - op->dev.map_seen);
+      op->map_stats.map_dropped_total += op->map_stats.map_dropped;
+      op->dev.map_seen = (uint32_t)(seen >> 32);
     }
     if (op->dev.having.n && op->dev.hv_ran) {
       // the changelog filter's kept rows came back with the same fetch
@@ -1008,6 +1169,15 @@ extern "C" int hsg_op_stats(const hsg_op *op, hsg_stats *out) {
   *out = op->stats;
   return HSG_OK;
 }
+
+extern "C" int hsg_op_map_stats(const hsg_op *op, hsg_map_stats *out) {
+  if (!op || !out) return HSG_E_INVALID;
+  wait_idle(op);
+  *out = op->map_stats;
+  return HSG_OK;
+}
+
+extern "C" int hsg_map_grid_threads(void) { return hsg::kMapGrid * hsg::kMapThreads; }
 
 namespace hsg {
 // For the sink encoder (sink.cpp): the op's device and which changelog

@@ -89,6 +89,17 @@ struct OpDevice {
   const hsg_batch *where_staged = nullptr;  // the batch of this push stage_batch already filtered
   Batch where_kb = {};                      // ... and what it resolved to
   uint64_t where_seen = 0;      // the cumulative masked-record count at the last push's end (kWhereWord)
+  // Computed columns (k_map.hip): an op with a map (map.n_exprs != 0) runs
+  // one pass in stage_batch, its WHERE program included (k_where is then not
+  // launched); the kernels' column j is expression j, an alias of a caller's
+  // column or an output the pass stores in map_col / map_valid. The pass keeps
+  // kWhereWord as two cumulative 32-bit halves: low WHERE drops, high strict
+  // map drops (map_seen: the high half at the last push's end).
+  MapPlan map = {};
+  MapProg map_prog = {};
+  int64_t *map_col[HSG_MAP_MAX_EXPRS] = {};
+  uint8_t *map_valid[HSG_MAP_MAX_EXPRS] = {};
+  uint32_t map_seen = 0;
   // HAVING pushdown (k_having.hip): the program over the op's aggregate
   // outputs (having.n == 0: none), run by finish_batch over the changelog
   // segment the batch appended, ahead of the fetch of the scalars. The push

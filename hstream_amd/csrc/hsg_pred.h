@@ -2,7 +2,8 @@
 // hstream_gpu.h hsg_where_ins), device side: the operand stack, the exact
 // i64 / f64 ordering and the instruction loop. k_where.hip runs it over a
 // staged batch's value columns, k_having.hip over a changelog segment's
-// aggregate columns; the semantics are written once, here.
+// aggregate columns, and k_map.hip runs its value half (value_step) to
+// compute the derived columns; the semantics are written once, here.
 //
 // The program arrives as a kernel argument, so opcodes, column numbers and the
 // value types (static: column type or constant kind) live in scalar registers
@@ -21,23 +22,34 @@ constexpr int D = HSG_WHERE_MAX_DEPTH;
 
 // The operand stack: v[0] is the top. Values are i64 or f64 bits, bools 0 / 1.
 // err: bit k = entry k is the error value (per lane); f: bit k = entry k is
-// f64 (uniform: derived from the program alone).
+// f64 (uniform: derived from the program alone); form: bit k = entry k's
+// literal-form bit (per lane; only the map pass reads it).
 struct Stack {
   uint64_t v[D];
   uint32_t err;
   uint32_t f;
-  __device__ __forceinline__ void push(uint64_t x, bool e, bool isf) {
+  uint32_t form;
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int k = 0; k < D; ++k) v[k] = 0;
+    err = 0;
+    f = 0;
+    form = 0;
+  }
+  __device__ __forceinline__ void push(uint64_t x, bool e, bool isf, bool fm = false) {
 #pragma unroll
     for (int k = D - 1; k > 0; --k) v[k] = v[k - 1];
     v[0] = x;
     err = (err << 1) | (e ? 1u : 0u);
     f = (f << 1) | (isf ? 1u : 0u);
+    form = (form << 1) | (fm ? 1u : 0u);
   }
   __device__ __forceinline__ void pop() {
 #pragma unroll
     for (int k = 0; k < D - 1; ++k) v[k] = v[k + 1];
     err >>= 1;
     f >>= 1;
+    form >>= 1;
   }
 };
 
@@ -68,42 +80,55 @@ __device__ __forceinline__ int cmp_vals(uint64_t a, bool af, uint64_t b, bool bf
   return c == 2 ? 2 : -c;
 }
 
-// One row through the program: cv[c] is the 8-byte word of column c (read for
-// the columns the program names only), bit c of `absent` says the column is
-// the error value for this row. True = the row is kept (the result is true,
-// not false and not the error).
+// The value half of the instruction set -- COL, I64, F64, ADD, SUB, MUL -- on
+// the stack: cv[c] is the 8-byte word of column c (read for the columns the
+// program names only), bit c of `absent` says the column is the error value
+// for this row, bit c of `cform` is its literal-form bit, bit c of `f64` its
+// type. False: `in` is none of these (the stack is untouched).
+template <int NC>
+__device__ __forceinline__ bool value_step(Stack &st, const hsg_where_ins &in, uint32_t f64, const uint64_t (&cv)[NC],
+                                           uint32_t absent, uint32_t cform) {
+  const int32_t op = in.op;
+  if (op == HSG_W_COL) {
+    const int32_t c = in.arg;
+    uint64_t x = 0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) x = c == k ? cv[k] : x;
+    st.push(x, (absent >> c) & 1u, (f64 >> c) & 1u, (cform >> c) & 1u);
+  } else if (op == HSG_W_I64 || op == HSG_W_F64) {
+    // (a map's constants carry their literal-form bit in `arg`)
+    st.push((uint64_t)in.imm.i, false, op == HSG_W_F64, in.arg & 1);
+  } else if (op <= HSG_W_MUL) {
+    // value value -> value: i64 wraps, anything with an f64 is f64
+    const uint64_t r = st.v[0], l = st.v[1];
+    const bool rf = st.f & 1u, lf = (st.f >> 1) & 1u;
+    const bool e = (st.err & 3u) != 0;
+    const bool fm = (st.form & 3u) != 0;
+    uint64_t o;
+    if (!lf && !rf) {
+      o = op == HSG_W_ADD ? l + r : (op == HSG_W_SUB ? l - r : l * r);
+    } else {
+      const double x = lf ? as_f64(l) : (double)(int64_t)l, y = rf ? as_f64(r) : (double)(int64_t)r;
+      o = as_u64(op == HSG_W_ADD ? x + y : (op == HSG_W_SUB ? x - y : x * y));
+    }
+    st.pop();
+    st.pop();
+    st.push(o, e, lf || rf, fm);
+  } else {
+    return false;
+  }
+  return true;
+}
+
+// One row through the program (cv, absent: value_step). True = the row is
+// kept (the result is true, not false and not the error).
 template <int NC>
 __device__ __forceinline__ bool eval(const WhereProg &p, const uint64_t (&cv)[NC], uint32_t absent) {
   Stack st;
-#pragma unroll
-  for (int k = 0; k < D; ++k) st.v[k] = 0;
-  st.err = 0;
-  st.f = 0;
+  st.clear();
   for (int pc = 0; pc < p.n; ++pc) {
     const int32_t op = p.ins[pc].op;
-    if (op == HSG_W_COL) {
-      const int32_t c = p.ins[pc].arg;
-      uint64_t x = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) x = c == k ? cv[k] : x;
-      st.push(x, (absent >> c) & 1u, (p.f64 >> c) & 1u);
-    } else if (op == HSG_W_I64 || op == HSG_W_F64) {
-      st.push((uint64_t)p.ins[pc].imm.i, false, op == HSG_W_F64);
-    } else if (op <= HSG_W_MUL) {
-      // value value -> value: i64 wraps, anything with an f64 is f64
-      const uint64_t r = st.v[0], l = st.v[1];
-      const bool rf = st.f & 1u, lf = (st.f >> 1) & 1u;
-      const bool e = (st.err & 3u) != 0;
-      uint64_t o;
-      if (!lf && !rf) {
-        o = op == HSG_W_ADD ? l + r : (op == HSG_W_SUB ? l - r : l * r);
-      } else {
-        const double x = lf ? as_f64(l) : (double)(int64_t)l, y = rf ? as_f64(r) : (double)(int64_t)r;
-        o = as_u64(op == HSG_W_ADD ? x + y : (op == HSG_W_SUB ? x - y : x * y));
-      }
-      st.pop();
-      st.pop();
-      st.push(o, e, lf || rf);
+    if (value_step(st, p.ins[pc], p.f64, cv, absent, 0u)) {
     } else if (op <= HSG_W_GE) {
       // value value -> bool; error if either operand is
       const int c = cmp_vals(st.v[1], (st.f >> 1) & 1u, st.v[0], st.f & 1u);

@@ -44,6 +44,64 @@ void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_type
 
 void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a);
 
+// ---- computed columns (k_map.hip) ---------------------------------------------
+// The op's map (include/hstream_gpu.h hsg_map_expr) as the pass runs it: the
+// value programs of the expressions the pass has work for, concatenated. An
+// expression that is a single COL is an alias (MapPlan::alias) and is
+// here only when it is strict, for its error bit. The op's WHERE program, if
+// any, travels in the same argument and runs first.
+constexpr int kMapThreads = 256;
+// one resident round of workgroups: kMapGroupsPerCU per CU of 256 CUs, from
+// the kernel's reported occupancy
+constexpr int kMapGroupsPerCU = 7;
+constexpr int kMapGrid = 256 * kMapGroupsPerCU;
+
+struct MapProg {
+  WhereProg where;                     // where.n == 0: no filter; where.cols / f64 as k_where reads them
+  int32_t n_ins;                       // instructions of all runs together
+  int32_t n_runs;                      // expressions evaluated
+  uint32_t cols;                       // bit c: WHERE or an expression names column c
+  uint32_t forms;                      // 1: HSG_OPF_LITERAL_FORMS, the derived valid bytes carry bit 1
+  int32_t end[HSG_MAP_MAX_EXPRS];      // run r is ins[end[r-1] .. end[r])
+  int32_t out[HSG_MAP_MAX_EXPRS];      // the output it stores (MapArgs::ocol), -1: none (a strict alias)
+  uint32_t strict;                     // bit r: run r is HSG_MAP_STRICT
+  uint32_t f64;                        // bit c: column c is HSG_F64
+  // (I64 / F64 constants carry their literal-form bit in `arg`)
+  hsg_where_ins ins[HSG_MAP_MAX_INS];
+};
+
+struct MapArgs {
+  uint64_t n;
+  const uint32_t *key;                 // staged keys
+  uint32_t *out;                       // masked keys (op-owned; may be `key`), null: the keys stay as they are
+  const int64_t *col[kMaxCols];        // the batch's columns (the caller's numbering)
+  const uint8_t *valid[kMaxCols];      // null = all present
+  int64_t *ocol[HSG_MAP_MAX_EXPRS];    // computed outputs (op-owned staging)
+  uint8_t *ovalid[HSG_MAP_MAX_EXPRS];  // null: every byte would be 1, none is written
+  // two cumulative 32-bit counts: [0] += keyed records WHERE masked, [1] +=
+  // keyed records WHERE kept and a strict expression dropped
+  unsigned int *dropped;
+};
+
+// What the host keeps of the map beside the kernel's program.
+struct MapPlan {
+  int32_t n_exprs = 0;                    // 0: the op has no map
+  int32_t n_out = 0;                      // computed outputs
+  int32_t alias[HSG_MAP_MAX_EXPRS] = {};  // expression j is the caller's column alias[j]; -1: computed
+  int32_t ocol[HSG_MAP_MAX_EXPRS] = {};   // ... or output ocol[j] of the pass
+  uint32_t reads[HSG_MAP_MAX_EXPRS] = {}; // the columns expression j names
+  bool const_form[HSG_MAP_MAX_EXPRS] = {};// expression j holds a constant whose literal-form bit is 1
+  bool keys = false;                      // the pass writes keys (a WHERE program or a strict expression)
+};
+
+// Type-check a map (hsg_map_check): HSG_OK with out_types (may be null), or HSG_E_INVALID with err set.
+int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, int32_t *out_types,
+              std::string &err);
+// (checked map; `where` compiled or n == 0) -> MapProg + MapPlan
+void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, bool forms,
+                 const WhereProg &where, MapProg &out, MapPlan &plan);
+void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a);
+
 // ---- HAVING pushdown (k_having.hip) ------------------------------------------
 // The same program over an op's changelog rows: column c is aggregate c of the
 // op (WhereProg::cols / f64 are 32-bit masks, kMaxAggs is 16).

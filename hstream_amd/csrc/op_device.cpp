@@ -220,6 +220,7 @@ int op_device_reset(OpDevice &d, const hsg_op_config &cfg, const Program &prog, 
   d.ovf_rows = 0;  // the clear below empties the overflow rows with the regions
   d.sc_clean = false;
   d.where_seen = 0;
+  d.map_seen = 0;
   if (cfg.window_kind == HSG_SESSION) {
     int rc = session_device_reset(d, err);
     if (rc != HSG_OK) return rc;
@@ -292,10 +293,19 @@ int op_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &prog, u
   DTRY(dalloc(&d.st_key, d.batch_cap));
   DTRY(dalloc(&d.st_ts, d.batch_cap));
   // (the caller's columns: an op with a WHERE program stages the columns only
-  // its filter reads too, hsg_api.cpp hsg_op_create_where)
-  for (int c = 0; c < d.user_cols; ++c) {
+  // its filter reads too, hsg_api.cpp hsg_op_create_where). On a sharded op
+  // the classic exchange unpacks the records it receives into the same arrays
+  // by the kernels' numbering (exchange.cpp push_sharded_classic), and a map
+  // can have more expressions than the batch has columns: both counts hold.
+  const int st_cols = sharded && cfg.n_cols > d.user_cols ? cfg.n_cols : d.user_cols;
+  for (int c = 0; c < st_cols; ++c) {
     DTRY(dalloc(&d.st_col[c], d.batch_cap));
     DTRY(dalloc(&d.st_valid[c], d.batch_cap));
+  }
+  // the map's computed outputs (k_map.hip): a rank maps its own slice, ahead of the exchange
+  for (int o = 0; o < d.map.n_out; ++o) {
+    DTRY(dalloc(&d.map_col[o], batch_cap));
+    DTRY(dalloc(&d.map_valid[o], batch_cap));
   }
   uint64_t rows = cfg.state_capacity ? cfg.state_capacity : (1ull << 21);
   d.cap = next_pow2(rows * 2);  // load factor <= 1/2
@@ -386,6 +396,10 @@ void op_device_free(OpDevice &d) {
   for (int c = 0; c < kMaxCols; ++c) {
     dfree(d.st_col[c]);
     dfree(d.st_valid[c]);
+  }
+  for (int o = 0; o < HSG_MAP_MAX_EXPRS; ++o) {
+    dfree(d.map_col[o]);
+    dfree(d.map_valid[o]);
   }
   dfree(d.st_seq);
   dfree(d.st_wm);
@@ -536,6 +550,7 @@ static int widen_batch(OpDevice &d, const hsg_batch *b, const void *k16, const v
 }
 
 static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set);
+static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set);
 
 // Resolve the batch into device pointers, copying host arrays into staging
 // (or taking the ones op_prestage queued for it). The valid bytes go to the
@@ -550,13 +565,15 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
 // columns are then the ones an aggregate reads (OpDevice::col_map).
 int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
   // (a sharded push that falls back from the fast exchange stages its batch a
-  // second time: the filter ran, and counted, the first time)
-  if (d.where.n && d.where_staged == b) {
+  // second time: the filter / the map ran, and counted, the first time)
+  const bool staged_pass = d.where.n || d.map.n_exprs;
+  if (staged_pass && d.where_staged == b) {
     kb = d.where_kb;
     return HSG_OK;
   }
   int rc = stage_batch_raw(d, b, kb, err, staged_set);
-  if (rc != HSG_OK || !d.where.n) return rc;
+  if (rc != HSG_OK || !staged_pass) return rc;
+  if (d.map.n_exprs) return stage_map(d, b, kb, err, staged_set);
   if (kb.n) {
     WhereArgs w;
     memset(&w, 0, sizeof(w));
@@ -578,6 +595,63 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
     const bool on = c < d.n_cols;
     kb.col[c] = on ? in.col[d.col_map[c]] : nullptr;
     kb.valid[c] = on ? in.valid[d.col_map[c]] : nullptr;
+  }
+  d.where_staged = b;
+  d.where_kb = kb;
+  return HSG_OK;
+}
+
+// The op's map over the staged batch (OpDevice::map, k_map.hip): one pass
+// runs the WHERE program, if the op has one, and every expression that is
+// not a caller's column as it is. The keys are written (as the filter writes
+// them, never into a caller's array) only when the pass can drop a record;
+// the computed outputs and their valid bytes go to the op's own staging, the
+// valid bytes only where one could be other than 1: an input of the
+// expression has a valid array, or the op keeps literal forms and the
+// expression holds a constant that is not integral. The kernels' column j is
+// then expression j.
+static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
+  const MapPlan &m = d.map;
+  bool need_valid[HSG_MAP_MAX_EXPRS] = {};
+  for (int j = 0; j < m.n_exprs; ++j) {
+    need_valid[j] = d.forms && m.const_form[j];
+    for (int c = 0; c < d.user_cols; ++c) need_valid[j] |= ((m.reads[j] >> c) & 1u) && kb.valid[c];
+  }
+  if (kb.n) {
+    MapArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = kb.n;
+    a.key = kb.key;
+    if (m.keys) {
+      const bool own = kb.key == d.st_key || (staged_set >= 0 && kb.key == d.pre[staged_set].key);
+      a.out = own ? const_cast<uint32_t *>(kb.key) : d.st_key;
+    }
+    for (int c = 0; c < d.user_cols; ++c) {
+      a.col[c] = kb.col[c];
+      a.valid[c] = kb.valid[c];
+    }
+    for (int j = 0; j < m.n_exprs; ++j) {
+      if (m.alias[j] >= 0) continue;
+      a.ocol[m.ocol[j]] = d.map_col[m.ocol[j]];
+      a.ovalid[m.ocol[j]] = need_valid[j] ? d.map_valid[m.ocol[j]] : nullptr;
+    }
+    a.dropped = (unsigned int *)&d.sc->scratch[kWhereWord];
+    launch_map(d.stream, d.map_prog, a);
+    DTRY(hipGetLastError());
+    if (a.out) kb.key = a.out;
+  }
+  Batch in = kb;
+  for (int j = 0; j < kMaxCols; ++j) {
+    kb.col[j] = nullptr;
+    kb.valid[j] = nullptr;
+    if (j >= m.n_exprs) continue;
+    if (m.alias[j] >= 0) {
+      kb.col[j] = in.col[m.alias[j]];
+      kb.valid[j] = in.valid[m.alias[j]];
+    } else {
+      kb.col[j] = d.map_col[m.ocol[j]];
+      kb.valid[j] = need_valid[j] ? d.map_valid[m.ocol[j]] : nullptr;
+    }
   }
   d.where_staged = b;
   d.where_kb = kb;

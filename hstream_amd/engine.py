@@ -50,6 +50,16 @@ def load_library(path=LIB_PATH):
     L.hsg_op_create_filtered.argtypes = [vp, P(abi.hsg_op_config), P(abi.hsg_where_ins), C.c_int32,
                                          P(abi.hsg_where_ins), C.c_int32, P(vp)]
     L.hsg_op_create_filtered.restype = C.c_int
+    L.hsg_map_check.argtypes = [P(abi.hsg_map_expr), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_char_p,
+                                C.c_size_t]
+    L.hsg_map_check.restype = C.c_int
+    L.hsg_op_create_mapped.argtypes = [vp, P(abi.hsg_op_config), P(abi.hsg_map_expr), C.c_int32,
+                                       P(abi.hsg_where_ins), C.c_int32, P(abi.hsg_where_ins), C.c_int32, P(vp)]
+    L.hsg_op_create_mapped.restype = C.c_int
+    L.hsg_op_map_stats.argtypes = [vp, P(abi.hsg_map_stats)]
+    L.hsg_op_map_stats.restype = C.c_int
+    L.hsg_map_grid_threads.argtypes = []
+    L.hsg_map_grid_threads.restype = C.c_int
     L.hsg_having_tile_rows.argtypes = []
     L.hsg_having_tile_rows.restype = C.c_int
     L.hsg_op_stats.argtypes = [vp, P(abi.hsg_stats)]
@@ -113,6 +123,24 @@ def having_check(program, spec: OpSpec):
     buf = C.create_string_buffer(256)
     rc = L.hsg_having_check(prog, n, C.byref(cfg), buf, len(buf))
     return rc, buf.value.decode()
+
+
+def map_check(exprs, col_types):
+    """hsg_map_check (host only, no GPU): (status, message, out_types) for a
+    map -- abi.MapExpr, or bare programs -- over value columns of the given
+    types."""
+    L = load_library()
+    arr, n, keep = abi.map_array(exprs)
+    types = (C.c_int32 * max(1, len(col_types)))(*col_types)
+    out = (C.c_int32 * max(1, n))()
+    buf = C.create_string_buffer(256)
+    rc = L.hsg_map_check(arr, n, types, len(col_types), out, buf, len(buf))
+    return rc, buf.value.decode(), list(out)[:n] if rc == abi.HSG_OK else None
+
+
+def map_grid_threads() -> int:
+    """Threads of one resident round of the map pass's grid (hsg_map_grid_threads)."""
+    return load_library().hsg_map_grid_threads()
 
 
 def having_tile_rows() -> int:
@@ -202,7 +230,13 @@ class GpuOp(OpHandle):
         cfg, keep = spec.to_config()
         h = C.c_void_p()
         what = "hsg_op_create"
-        if spec.having is not None or spec.where is not None:
+        if spec.map:
+            what = "hsg_op_create_mapped"
+            marr, mn, mkeep = abi.map_array(spec.map)
+            wprog, wn = abi.where_array(spec.where) if spec.where is not None else (None, 0)
+            hprog, hn = abi.where_array(spec.having) if spec.having is not None else (None, 0)
+            rc = engine._lib.hsg_op_create_mapped(engine._h, C.byref(cfg), marr, mn, wprog, wn, hprog, hn, C.byref(h))
+        elif spec.having is not None or spec.where is not None:
             what = "hsg_op_create_filtered"
             wprog, wn = abi.where_array(spec.where) if spec.where is not None else (None, 0)
             hprog, hn = abi.where_array(spec.having) if spec.having is not None else (None, 0)
@@ -310,6 +344,12 @@ class GpuOp(OpHandle):
                 continue
             self._check(rc, "table_join")
             return truncate(arrs, got)
+
+    def map_stats(self) -> dict:
+        """hsg_op_map_stats: the map's counters (zeros for an op without one)."""
+        s = abi.hsg_map_stats()
+        self._check(self._lib.hsg_op_map_stats(self._h, C.byref(s)), "op_map_stats")
+        return s.as_dict()
 
     def stats(self) -> dict:
         s = abi.hsg_stats()

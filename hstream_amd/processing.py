@@ -155,11 +155,26 @@ class KeyDict:
 # aggregates: the SQL components the codegen builds (Codegen.hs:399-469)
 # ---------------------------------------------------------------------------
 @dataclass(frozen=True)
+class Expr:
+    """A value expression of the SELECT list (hstream_amd.sql RExprBinOp /
+    RExprConst / RExprCol tree) in an aggregate's place of a field name, and
+    which of the fields it reads carry decimals (f64 columns). The op's map
+    pass evaluates it per record on the GPU (hsg_op_create_mapped)."""
+
+    tree: Any
+    float_fields: Tuple[str, ...] = ()
+
+    def __str__(self):
+        return self.tree.name
+
+
+@dataclass(frozen=True)
 class Agg:
     kind: int                 # abi.HSG_COUNT_ALL ...
-    field: Optional[str] = None
+    field: Any = None         # a field name, or an Expr
     alias: Optional[str] = None
     is_float: bool = False    # the column's type (numbers with decimals -> f64)
+    strict: bool = False      # an Expr only: a record whose expression is the error value is dropped (HSG_MAP_STRICT)
 
     @property
     def name(self):
@@ -194,9 +209,9 @@ def AVG(f, alias=None, is_float=False):
     return Agg(abi.HSG_AVG, f, alias, is_float)
 
 
-def LAST(f, alias=None, is_float=False):
+def LAST(f, alias=None, is_float=False, strict=False):
     """A non-aggregate SELECT column: the last record's value (Codegen.hs:463-469)."""
-    return Agg(abi.HSG_LAST, f, alias, is_float)
+    return Agg(abi.HSG_LAST, f, alias, is_float, strict)
 
 
 @dataclass
@@ -303,14 +318,45 @@ class Table:
         self.aggs = list(aggs)
         self.mat = materialized
         fields: List[Tuple[str, bool]] = []
+        # the aggregates' columns: a field, or a value expression the op's map
+        # pass computes (hsg_op_create_mapped); with an expression among them
+        # every column is one of the map's, a bare field a one-instruction one
+        acols: List[Tuple[Any, bool, bool]] = []
         for a in self.aggs:
-            if a.kind != abi.HSG_COUNT_ALL and (a.field, a.is_float) not in fields:
+            if a.kind == abi.HSG_COUNT_ALL:
+                continue
+            if (a.field, a.is_float, a.strict) not in acols:
+                acols.append((a.field, a.is_float, a.strict))
+            if not isinstance(a.field, Expr) and (a.field, a.is_float) not in fields:
                 fields.append((a.field, a.is_float))
-        col_of = {fk: i for i, fk in enumerate(fields)}
+        mapped = any(isinstance(f, Expr) for f, _, _ in acols)
+        if mapped:
+            col_of = {a: i for i, a in enumerate(acols)}
+        else:
+            col_of = {(f, fl, st): i for i, (f, fl) in enumerate(fields) for st in (False, True)}
         # a column read only by COUNT(col) counts any present value (Codegen.hs:412-422);
         # SUM / MIN / MAX / AVG / LAST need a Number (Codegen.hs:423-461)
         self.numeric = [any(a.kind not in (abi.HSG_COUNT_ALL, abi.HSG_COUNT) and (a.field, a.is_float) == fk
                             for a in self.aggs) for fk in fields]
+        if mapped:
+            # the fields the expressions read follow as columns of the batch;
+            # each must hold a Number (a present non-number drops the record at
+            # ingest, as for WHERE fields: the program computes numbers only)
+            from . import sql
+            for f, _, _ in acols:
+                if not isinstance(f, Expr):
+                    continue
+                for name in sql.where_fields(f.tree):
+                    names = [x for x, _ in fields]
+                    if name in names:
+                        self.numeric[names.index(name)] = True
+                    else:
+                        fields.append((name, name in f.float_fields))
+                        self.numeric.append(True)
+            names = [x for x, _ in fields]
+            spec.map = [abi.MapExpr(sql.compile_expr(f.tree, names, key_field=grouped.key_field),
+                                    abi.HSG_MAP_STRICT if st else 0) if isinstance(f, Expr)
+                        else abi.MapExpr([(abi.HSG_W_COL, fields.index((f, fl)))]) for f, fl, st in acols]
         self.where = where
         if where is not None:
             # the filter runs in the op (hsg_op_create_where): the fields only it
@@ -336,7 +382,8 @@ class Table:
         self.fields = fields
         self._decoder = None
         spec.col_types = [abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in fields]
-        spec.aggs = [(a.kind, col_of[(a.field, a.is_float)] if a.kind != abi.HSG_COUNT_ALL else 0) for a in self.aggs]
+        spec.aggs = [(a.kind, col_of[(a.field, a.is_float, a.strict)] if a.kind != abi.HSG_COUNT_ALL else 0)
+                     for a in self.aggs]
         spec.state_capacity = materialized.state_capacity
         spec.out_capacity = materialized.out_capacity
         self.spec = spec

@@ -17,6 +17,9 @@ the BNFC parser/validator are out of scope).
                      the GPU ahead of the aggregate (include/hstream_gpu.h
                      hsg_where_ins), where the reference chains genFilterNode
                      in front of it (Codegen.hs:540)
+  compile_expr       a value expression of the SELECT list as the postfix value
+                     program the op's map pass runs per record (include/
+                     hstream_gpu.h hsg_map_expr): genRExprValue, Codegen.hs:290-301
   compile_having     the HAVING condition as the same program over the
                      aggregates' aliases, run over the rows the op emits,
                      where the reference chains genFilteRNodeFromHaving
@@ -186,6 +189,9 @@ def _expr_value(e, value):
     raise TypeError(f"unsupported expression {e!r}")
 
 
+expr_value = _expr_value
+
+
 def gen_filter_r(cond, value) -> bool:
     """genFilterR (Codegen.hs:303-341) for one record's value object. Python
     evaluates as eagerly as Haskell evaluates lazily here: `or` / `and` look at
@@ -236,6 +242,69 @@ def where_fields(cond) -> List[str]:
     return out
 
 
+def _emit_expr(e, fields, key_field, what, prog) -> int:
+    """Append the value expression e to prog (postfix); returns the stack
+    depth it needs. ValueError for what the program cannot say."""
+    if isinstance(e, RExprCol):
+        name = _field_name(e)
+        if key_field is not None and name == key_field:
+            raise ValueError(f"{what} on the group key {name!r} is not pushed down")
+        if name not in fields:
+            raise ValueError(f"{what} reads {name!r}, which is not " +
+                             ("an alias of the SELECT list" if what == "HAVING" else "a value column"))
+        prog.append((abi.HSG_W_COL, fields.index(name)))
+        return 1
+    if isinstance(e, RExprConst):
+        c = e.constant
+        if not _is_number(c):
+            raise ValueError(f"constant {c!r} is not a number: not pushed down")
+        if isinstance(c, int):
+            if not -2**63 <= c < 2**63:
+                raise ValueError(f"integer constant {c} does not fit an i64")
+            prog.append((abi.HSG_W_I64, c))
+        else:
+            if not math.isfinite(c):
+                raise ValueError("non-finite constant")
+            prog.append((abi.HSG_W_F64, c))
+        return 1
+    if isinstance(e, RExprBinOp):
+        if e.op not in _BIN_OPS:
+            raise ValueError(f"operator {e.op} is not pushed down")
+        d1 = _emit_expr(e.expr1, fields, key_field, what, prog)
+        d2 = _emit_expr(e.expr2, fields, key_field, what, prog)
+        prog.append((_BIN_OPS[e.op],))
+        return max(d1, 1 + d2)
+    if isinstance(e, RExprUnaryOp):
+        raise ValueError(f"unary function {e.op} is not pushed down")
+    raise ValueError(f"unsupported expression {e!r}")
+
+
+def compile_expr(e, fields: Sequence[str], key_field: Optional[str] = None, what: str = "SELECT") -> List[Tuple]:
+    """A value expression (RExprCol / RExprConst / RExprBinOp tree) as a
+    postfix value program, [(op,) | (op, arg)], over value columns named
+    `fields` (column c = fields[c]): one expression of the op's map. ValueError
+    for what the program cannot say, the same list as compile_where's."""
+    prog: List[Tuple] = []
+    depth = _emit_expr(e, list(fields), key_field, what, prog)
+    if len(prog) > abi.HSG_MAP_MAX_INS:
+        raise ValueError(f"{what} expression needs {len(prog)} instructions (max {abi.HSG_MAP_MAX_INS})")
+    if depth > abi.HSG_WHERE_MAX_DEPTH:
+        raise ValueError(f"{what} expression needs a stack of {depth} (max {abi.HSG_WHERE_MAX_DEPTH})")
+    return prog
+
+
+def expr_is_float(e, float_fields=()) -> bool:
+    """The static type of a value expression: f64 iff a field that carries
+    decimals or a float constant takes part."""
+    if isinstance(e, RExprCol):
+        return _field_name(e) in float_fields
+    if isinstance(e, RExprConst):
+        return isinstance(e.constant, float)
+    if isinstance(e, RExprBinOp):
+        return expr_is_float(e.expr1, float_fields) or expr_is_float(e.expr2, float_fields)
+    return False
+
+
 def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, what: str = "WHERE") -> List[Tuple]:
     """The condition as a postfix hsg_where_ins program, [(op,) | (op, arg)],
     over value columns named `fields` (column c = fields[c]). ValueError for
@@ -246,39 +315,8 @@ def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, 
     fields = list(fields)
     prog: List[Tuple] = []
 
-    def expr(e) -> int:  # emits e, returns the stack depth it needs
-        if isinstance(e, RExprCol):
-            name = _field_name(e)
-            if key_field is not None and name == key_field:
-                raise ValueError(f"{what} on the group key {name!r} is not pushed down")
-            if name not in fields:
-                raise ValueError(f"{what} reads {name!r}, which is not " +
-                                 ("a value column" if what == "WHERE" else "an alias of the SELECT list"))
-            prog.append((abi.HSG_W_COL, fields.index(name)))
-            return 1
-        if isinstance(e, RExprConst):
-            c = e.constant
-            if not _is_number(c):
-                raise ValueError(f"constant {c!r} is not a number: not pushed down")
-            if isinstance(c, int):
-                if not -2**63 <= c < 2**63:
-                    raise ValueError(f"integer constant {c} does not fit an i64")
-                prog.append((abi.HSG_W_I64, c))
-            else:
-                if not math.isfinite(c):
-                    raise ValueError("non-finite constant")
-                prog.append((abi.HSG_W_F64, c))
-            return 1
-        if isinstance(e, RExprBinOp):
-            if e.op not in _BIN_OPS:
-                raise ValueError(f"operator {e.op} is not pushed down")
-            d1 = expr(e.expr1)
-            d2 = expr(e.expr2)
-            prog.append((_BIN_OPS[e.op],))
-            return max(d1, 1 + d2)
-        if isinstance(e, RExprUnaryOp):
-            raise ValueError(f"unary function {e.op} is not pushed down")
-        raise ValueError(f"unsupported expression {e!r}")
+    def expr(e) -> int:
+        return _emit_expr(e, fields, key_field, what, prog)
 
     def search(c) -> int:
         if isinstance(c, RCondOp):
@@ -331,10 +369,20 @@ def compile_having(cond, aggs: Sequence) -> List[Tuple]:
 
 # SELECT items: ("COUNT(*)",) / ("COUNT", col) / ("SUM", col) / ("MIN", col) /
 # ("MAX", col) / ("AVG", col) / ("COL", col); optional alias as last element.
+# col: a field name, or a value expression (RExprCol / RExprConst / RExprBinOp).
 SelItem = Tuple
 
 
-def gen_aggregate_components(sel: List[SelItem], float_fields=()) -> List[P.Agg]:
+def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Optional[str] = None) -> List[P.Agg]:
+    """genAggregateComponents (Codegen.hs:393-469). Where an item takes a
+    column name it also takes a value expression (RExprBinOp / RExprConst /
+    RExprCol tree): ("COL", expr) is genAggregateComponentsFromDerivedCol
+    (Codegen.hs:463-469), the last record's genRExprValue, strict as the
+    reference is (a record whose expression throws is dropped); an aggregate
+    over an expression is this engine's, as AVG is, and skips such a record.
+    The op's map pass evaluates the expression on the GPU. A tree that is just
+    a column is the plain column. ValueError, and the query stays on the host,
+    for what compile_expr cannot say."""
     out = []
     for item in sel:
         kind, *rest = item
@@ -346,21 +394,33 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=()) -> List[P.Agg]
             continue
         col = rest[0]
         alias = rest[1] if len(rest) > 1 else None
-        fl = col in float_fields
+        strict = False
+        if isinstance(col, RExprCol):
+            col = _field_name(col)
+        if isinstance(col, str):
+            fl = col in float_fields
+            cname = col
+        else:
+            names = where_fields(col)
+            compile_expr(col, names, key_field)  # raises for what the program cannot say
+            fl = expr_is_float(col, float_fields)
+            cname = col.name
+            col = P.Expr(col, tuple(f for f in names if f in float_fields))
+            strict = kind == "COL"
         if kind == "COUNT":
-            out.append(P.COUNT(col, alias or f"COUNT({col})"))
+            out.append(P.COUNT(col, alias or f"COUNT({cname})"))
         elif kind == "SUM":
-            out.append(P.SUM(col, alias or f"SUM({col})", fl))
+            out.append(P.SUM(col, alias or f"SUM({cname})", fl))
         elif kind == "MIN":
-            out.append(P.MIN(col, alias or f"MIN({col})", fl))
+            out.append(P.MIN(col, alias or f"MIN({cname})", fl))
         elif kind == "MAX":
-            out.append(P.MAX(col, alias or f"MAX({col})", fl))
+            out.append(P.MAX(col, alias or f"MAX({cname})", fl))
         elif kind == "AVG":
             # the reference throws "Unsupported aggregate function" (Codegen.hs:462);
             # this engine defines AVG = SUM(col) / COUNT(col)
-            out.append(P.AVG(col, alias or f"AVG({col})", fl))
+            out.append(P.AVG(col, alias or f"AVG({cname})", fl))
         elif kind == "COL":
-            out.append(P.LAST(col, alias or col, fl))
+            out.append(P.LAST(col, alias or cname, fl, strict))
         else:
             raise ValueError(f"Unsupported aggregate function: {kind}")
     return out
@@ -380,7 +440,7 @@ def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.H
     554-559 never looks at it) and for HSG_EMIT_NONE, which emits nothing, it
     is dropped silently."""
     grouped = P.groupBy(engine, group_by.column)
-    aggs = gen_aggregate_components(sel, float_fields)
+    aggs = gen_aggregate_components(sel, float_fields, key_field=group_by.column)
     mat = P.Materialized(state_capacity=state_capacity)
     if where is not None:
         where = P.Where(where, float_fields)

@@ -201,6 +201,53 @@ typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } 
  * compacted: the changelog room check ahead of a push (HSG_E_CAPACITY) stays
  * the batch's worst case before the filter. */
 
+/* Computed columns: the SELECT list's value expressions, evaluated per record
+ * ahead of the aggregate. The reference keeps, per group, genRExprValue of
+ * the last record for any value expression of the SELECT list
+ * (genAggregateComponentsFromDerivedCol, Codegen.hs:463-469); aggregates over
+ * arithmetic, SUM(price * qty), are this engine's, as HSG_AVG is.
+ *
+ * A map is a list of value programs: hsg_where_ins sequences of HSG_W_COL,
+ * HSG_W_I64, HSG_W_F64, HSG_W_ADD, HSG_W_SUB and HSG_W_MUL only, each leaving
+ * exactly one value. COL arg names a column of the batch (cfg->n_cols,
+ * cfg->col_types), as in the WHERE program. Expression j defines the
+ * aggregates' column j: with a map, cfg->aggs[].column indexes the
+ * expressions, not the batch. An expression's type is static, i64 unless an
+ * f64 column or constant takes part, and the arithmetic is the WHERE
+ * program's (i64 wraps; with an f64 operand IEEE f64, one rounding per
+ * instruction).
+ *
+ * An expression that reads a column whose valid bit 0 is clear is the error
+ * value for that record. By default the derived column is then absent for
+ * the record (bit 0 of its valid byte is 0) and every aggregate over it
+ * leaves its accumulator alone, as for an absent bare column. With
+ * HSG_MAP_STRICT on the expression the record is dropped instead: its key
+ * becomes HSG_KEY_NONE after it has moved stream time, exactly as a WHERE
+ * drop (the reference's strict HashMap forces genRExprValue, getFieldByName
+ * throws inside aggregateF, and runTask goes on after
+ * updateTimestampInTaskContext, Processor.hs:139-143).
+ *
+ * Ops with HSG_OPF_LITERAL_FORMS take bit 1 of the derived valid byte from
+ * the operands: COL gives the input's bit 1, an I64 constant 0, an F64
+ * constant 1 iff it is not integral (2.0 is 2e0 to Scientific), ADD / SUB /
+ * MUL the OR of their operands (DESIGN.md 9 for the one case this misses).
+ * Without the flag bit 1 is 0.
+ *
+ * WHERE comes first, over the raw columns, then the map: a record WHERE
+ * dropped is not counted by the map. An expression that is a single COL is
+ * an alias: nothing is computed, the aggregates read the caller's column. */
+#define HSG_MAP_STRICT 1u
+#define HSG_MAP_MAX_EXPRS 8
+#define HSG_MAP_MAX_INS   64   /* all expressions together */
+typedef struct { const hsg_where_ins *prog; int32_t n; uint32_t flags; } hsg_map_expr;
+typedef struct {
+  uint64_t map_dropped;        /* keyed records of the last batch (this rank's ingest) that WHERE
+                                  kept and a strict expression dropped                          */
+  uint64_t map_dropped_total;
+  uint32_t computed_cols;      /* expressions the map pass computes and stores                  */
+  uint32_t aliased_cols;       /* expressions that are a caller's column (a single COL)         */
+} hsg_map_stats;
+
 typedef struct hsg_engine hsg_engine;
 typedef struct hsg_op hsg_op;
 
@@ -403,6 +450,34 @@ int  hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg
                             const hsg_where_ins *having, int32_t n_having, hsg_op **out);
 /* Rows of one compaction tile of the HAVING pass (tests size their segments by it). */
 int  hsg_having_tile_rows(void);
+/* Type-check a map (hsg_map_expr, above) against an op's value columns; pure
+ * host code (no GPU). HSG_OK, with out_types[j] (may be null) the static type
+ * of expression j, only when 1 <= n_exprs <= HSG_MAP_MAX_EXPRS, the programs
+ * hold at most HSG_MAP_MAX_INS instructions together, every opcode is one of
+ * COL / I64 / F64 / ADD / SUB / MUL, every program leaves exactly one value
+ * and never holds more than HSG_WHERE_MAX_DEPTH, every column is in range and
+ * every f64 constant is finite; else HSG_E_INVALID with a message in err that
+ * begins "map: " ("map: expr <j>: " for a fault of expression j). */
+int  hsg_map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols,
+                   int32_t *out_types, char *err, size_t err_len);
+/* hsg_op_create_filtered with a map of n_exprs expressions (n_exprs == 0:
+ * none; that is hsg_op_create_filtered). cfg->n_cols / col_types describe the
+ * batch, the WHERE program and the expressions number its columns alike, and
+ * cfg->aggs[].column indexes the expressions, typed as hsg_map_check types
+ * them; the HAVING program is checked against those types ("having: ..." in
+ * hsg_engine_last_error). The programs are copied and fixed for the op's
+ * life; hsg_op_reset keeps them. A map hsg_map_check refuses fails the
+ * creation with HSG_E_INVALID and that message in hsg_engine_last_error.
+ * Collective on a sharded engine, like hsg_op_create: each rank maps its own
+ * slice before the exchange, which then carries the derived columns only. */
+int  hsg_op_create_mapped(hsg_engine *eng, const hsg_op_config *cfg, const hsg_map_expr *exprs, int32_t n_exprs,
+                          const hsg_where_ins *where, int32_t n_where,
+                          const hsg_where_ins *having, int32_t n_having, hsg_op **out);
+/* The map's counters (hsg_stats keeps its size); zeros for an op without one. */
+int  hsg_op_map_stats(const hsg_op *op, hsg_map_stats *out);
+/* Threads of one resident round of the map pass's grid: a batch of more records
+ * strides (tests size a batch past it). */
+int  hsg_map_grid_threads(void);
 void hsg_op_destroy(hsg_op *op);
 int  hsg_op_reset(hsg_op *op);            /* drop all state and pending rows          */
 const char *hsg_last_error(const hsg_op *op);

@@ -151,13 +151,22 @@ def _join_gen(seed, n, nkeys=40, grid=5, span=40_000):
 
 
 JOIN_CASES = {"w100_50": (100, 50, 5), "w0_0": (0, 0, 1), "w250_0": (250, 0, 25)}
+# full-width record keys through join_owner, negative timestamps across a
+# multiple of 2^32 through the all-gather and the compaction: the generator of
+# tests/test_gpu_join_edges.py (a) at base -2^32, at (a)'s density
+JOIN_CASES["full_width_neg"] = (100, 50, "full_width")
 
 
 def _join_slices(case, G):
     """batches of the stream, each cut into G consecutive rank slices (rank
     order = arrival order); the second batch's slice of rank 0 is empty"""
     before, after, grid = JOIN_CASES[case]
-    side, key, jk, ts, h = _join_gen(before * 7 + after + grid, 12_000, grid=grid)
+    if grid == "full_width":
+        from test_gpu_join_edges import full_width_stream
+        side, key, jk, ts, h = full_width_stream(-2**32, n=12_000, span=16_000)
+        assert ts.min() < -2**32 < ts.max() < 0
+    else:
+        side, key, jk, ts, h = _join_gen(before * 7 + after + grid, 12_000, grid=grid)
     out = []
     for bi, s0 in enumerate(range(0, len(ts), 3_000)):
         b = [a[s0:s0 + 3_000] for a in (side, key, jk, ts, h)]

@@ -664,7 +664,8 @@ static int validate_config(const hsg_op_config *c, std::string &err, int32_t agg
 }
 
 uint64_t hsg_windows_per_record(const hsg_op_config &c) {
-  if (c.window_kind == HSG_HOPPING) return (uint64_t)((c.size_ms + c.advance_ms - 1) / c.advance_ms);
+  // ceil(size / advance); (size + advance - 1) would pass INT64_MAX for a size near it
+  if (c.window_kind == HSG_HOPPING) return (uint64_t)((c.size_ms - 1) / c.advance_ms + 1);
   return 1;
 }
 

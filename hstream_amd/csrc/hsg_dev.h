@@ -198,12 +198,38 @@ __device__ inline bool record_windows(const TwParams &p, int64_t ts, uint64_t &k
   return true;
 }
 
+// t + size + grace <= INT64_MAX (size, grace >= 0), without overflowing: no
+// window of a record at or before t has an end + grace that wraps
+__device__ inline bool tw_sum_fits(int64_t t, int64_t size, int64_t grace) {
+  return grace <= INT64_MAX - size && t <= INT64_MAX - size - grace;
+}
+
 // grace check of window k against the record's stream time (TimeWindowedStream.hs:92)
 __device__ inline bool window_accepted(const TwParams &p, uint64_t k, int64_t wm) {
   if (p.kind == HSG_UNWINDOWED) return true;
   int64_t ws = (int64_t)(k * (uint64_t)p.adv);
   int64_t we = (int64_t)((uint64_t)ws + (uint64_t)p.size);
   return wm < (int64_t)((uint64_t)we + (uint64_t)p.grace);
+}
+
+// The accepted windows of a record, as one run inside its windows [k_lo, k_hi]
+// (narrowed in place; `late` counts the refused ones). The leading windows may
+// have closed (end + grace <= stream time). The trailing ones may end so high
+// that end + grace passes INT64_MAX: the reference's Int64 sum wraps negative
+// there and refuses them too. Every kernel that lays a record's windows out
+// as a run (partition histogram and scatter, the per-record changelog's
+// offsets) takes it from here, so their counts agree. False: none accepted.
+__device__ inline bool accepted_run(const TwParams &p, int64_t wm, uint64_t &k_lo, uint64_t &k_hi, uint64_t &late) {
+  while (k_lo <= k_hi && !window_accepted(p, k_lo, wm)) {
+    ++k_lo;
+    ++late;
+  }
+  if (k_lo > k_hi) return false;
+  while (k_hi > k_lo && !window_accepted(p, k_hi, wm)) {
+    --k_hi;
+    ++late;
+  }
+  return true;
 }
 
 }  // namespace hsg

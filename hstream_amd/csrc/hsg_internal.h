@@ -351,13 +351,13 @@ inline bool batch_narrow(const hsg_batch *b) {
 
 // stream time: tile maxima -> exclusive tile prefix (+ epoch init)
 void launch_tile_stats(hipStream_t s, const Batch &b, int64_t *tile_max, int64_t *tile_min, uint64_t n_tiles);
-// grace >= 0: also decide sc->no_late for a time-window op
+// grace >= 0: also decide sc->no_late for a time-window op of window size `size`
 // window epoch from the first keyed record (ts >= 0) of the batch, when not
 // yet set: optimistic batches need no stream-time pass for it
 void launch_epoch_first(hipStream_t s, const Batch &b, int64_t adv, DevScalars *sc);
 void launch_tile_scan(hipStream_t s, const int64_t *tile_max, const int64_t *tile_min, int64_t *tile_prefix,
                       uint64_t n_tiles, int64_t wm_in, int64_t adv, bool set_epoch, DevScalars *sc,
-                      int64_t grace = -1);
+                      int64_t grace = -1, int64_t size = 0);
 
 // time windows, atomic hash aggregation (per-batch / none modes). rec_wm / seq
 // (optional) carry per-record stream time and global sequence after a key

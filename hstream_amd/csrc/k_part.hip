@@ -39,13 +39,8 @@ __device__ inline bool part_record(const TwParams &p, int64_t k_epoch, uint32_t 
   if (key == HSG_KEY_NONE) return false;
   uint64_t k_lo, k_hi;
   if (!record_windows(p, ts, k_lo, k_hi)) return false;
-  uint64_t k = k_lo;
-  while (k <= k_hi && !window_accepted(p, k, wm)) {
-    ++k;
-    ++late;
-  }
-  if (k > k_hi) return false;
-  int64_t a = (int64_t)k - k_epoch, z = (int64_t)k_hi - k_epoch;
+  if (!accepted_run(p, wm, k_lo, k_hi, late)) return false;
+  int64_t a = (int64_t)k_lo - k_epoch, z = (int64_t)k_hi - k_epoch;
   if (a < 0) {
     err |= ERR_RANGE;
     a = 0;
@@ -582,7 +577,9 @@ __device__ inline void part_decide_body(DevScalars *sc, const TwParams &p, int64
   const int64_t amin = mn ? (int64_t)(~mn ^ 0x8000000000000000ull) : INT64_MAX;
   const int64_t all = bmax > wm_in ? bmax : wm_in;
   sc->wm_out = all;
-  const bool ok = amin == INT64_MAX || amin > INT64_MAX - grace || all <= amin + grace;
+  // (a window end + grace past INT64_MAX wraps in the reference and the window
+  // is refused: such a batch takes the careful path, k_tile_scan)
+  const bool ok = amin == INT64_MAX || (tw_sum_fits(all, p.size, grace) && all <= amin + grace);
   sc->no_late = ok ? 1u : 0u;
   sc->redo = ok ? 0u : 1u;
   uint64_t pk = 0, kb = 0;

@@ -713,10 +713,9 @@ __global__ __launch_bounds__(kPrEmitThreads) void k_pr_emit(Batch bt, Program pr
         uint64_t k_lo, k_hi;
         if (record_windows(p, ts, k_lo, k_hi)) {
           const int64_t w = wm ? wm[i] : INT64_MIN;
-          uint64_t k = k_lo;
-          while (k <= k_hi && !window_accepted(p, k, w)) ++k;
-          if (k <= k_hi) {
-            int64_t lo = (int64_t)k - k_epoch, hi = (int64_t)k_hi - k_epoch;
+          uint64_t refused = 0;
+          if (accepted_run(p, w, k_lo, k_hi, refused)) {
+            int64_t lo = (int64_t)k_lo - k_epoch, hi = (int64_t)k_hi - k_epoch;
             if (lo < 0) lo = 0;
             if (hi > 0xFFFFFFFFll) hi = 0xFFFFFFFFll;
             if (lo <= hi) {
@@ -1504,10 +1503,9 @@ __device__ inline uint32_t pr_record_run(const Batch &bt, const TwParams &p, con
   uint64_t k_lo, k_hi;
   if (!record_windows(p, bt.ts[i], k_lo, k_hi)) return 0;
   const int64_t w = wm ? wm[i] : INT64_MIN;
-  uint64_t k = k_lo;
-  while (k <= k_hi && !window_accepted(p, k, w)) ++k;
-  if (k > k_hi) return 0;
-  int64_t lo = (int64_t)k - k_epoch, hi = (int64_t)k_hi - k_epoch;
+  uint64_t refused = 0;
+  if (!accepted_run(p, w, k_lo, k_hi, refused)) return 0;
+  int64_t lo = (int64_t)k_lo - k_epoch, hi = (int64_t)k_hi - k_epoch;
   if (lo < 0) lo = 0;
   if (hi > 0xFFFFFFFFll) hi = 0xFFFFFFFFll;
   if (lo > hi) return 0;

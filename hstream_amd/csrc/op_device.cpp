@@ -759,7 +759,7 @@ void launch_stream_time(OpDevice &d, const hsg_op_config &cfg, const Batch &kb, 
   launch_tile_stats(d.stream, kb, d.tile_max, d.tile_min, tiles);
   const bool tw = cfg.window_kind == HSG_TUMBLING || cfg.window_kind == HSG_HOPPING;
   launch_tile_scan(d.stream, d.tile_max, d.tile_min, d.tile_prefix, tiles, wm_in, adv, tw, d.sc,
-                   tw ? (cfg.grace_ms >= 0 ? cfg.grace_ms : 0) : -1);
+                   tw ? (cfg.grace_ms >= 0 ? cfg.grace_ms : 0) : -1, tw ? cfg.size_ms : 0);
 }
 
 // Copies the scalars to the host mirror, then (same stream, before the host

@@ -3,6 +3,7 @@ restatement against the independent pure-Python one on seeded inputs."""
 import numpy as np
 import pytest
 
+import axisgen
 import pyoracle
 import pyref
 from hstream_amd import abi
@@ -102,6 +103,122 @@ def test_cpp_oracle_matches_pyref(spec):
     assert len(st) == len(ex)
     for g, x in zip(st, ex):
         assert g[:3] == x[:3] and all(_close(a, b) for a, b in zip(g[3], x[3]))
+
+
+def _cross(spec, batches, wms=None):
+    """OracleOp against PyRefOp batch by batch: watermark, changelog, state."""
+    o, r = pyoracle.OracleOp(spec), pyref.PyRefOp(spec)
+    wm_o = wm_r = -1
+    for bi, (key, ts, cols, valid) in enumerate(batches):
+        if wms is not None and wms[bi] is not None:
+            wm_o = wm_r = wms[bi]
+        wm_o = o.push(key, ts, cols, valid, watermark=wm_o)
+        wm_r = r.push(key, ts, cols, valid, watermark=wm_r)
+        assert wm_o == wm_r
+        got = o.drain().tuples()
+        exp = [(k, s, e, v) for k, s, e, _, v in r.drain()]
+        if spec.emit_mode == abi.HSG_EMIT_PER_BATCH:
+            got, exp = sorted(got), sorted(exp)
+        assert len(got) == len(exp), bi
+        for g, x in zip(got, exp):
+            assert g[:3] == x[:3], (bi, g, x)
+            assert all(_close(a, b) for a, b in zip(g[3], x[3])), (g, x)
+    st = sorted(o.dump_state().tuples())
+    ex = sorted((k, s, e, v) for k, s, e, _, v in r.dump_state())
+    assert len(st) == len(ex)
+    for g, x in zip(st, ex):
+        assert g[:3] == x[:3] and all(_close(a, b) for a, b in zip(g[3], x[3])), (g, x)
+    o.close()
+    return st
+
+
+# ---- the time-axis generators (tests/axisgen.py), reduced: the reference side of
+# ---- tests/test_gpu_time_axis.py, proven without a GPU
+@pytest.mark.parametrize("emit", [abi.HSG_EMIT_PER_BATCH, abi.HSG_EMIT_PER_RECORD], ids=["batch", "changes"])
+@pytest.mark.parametrize("window", sorted(axisgen.WINDOWS))
+def test_axis_family_batches(window, emit):
+    """The three batches of a family case on a non-zero epoch (batch 0's first
+    keyed record in the middle, batch 2 before batch 0), messy and sorted."""
+    kind, kw = axisgen.window_kw(window)
+    spec = OpSpec(kind, emit, col_types=[abi.HSG_I64, abi.HSG_F64], aggs=ALL_AGG_SETS["mixed"], **kw)
+    for gen in ("messy", "uniform"):
+        shapes = axisgen.family(window, gen, 200, 7, 10, seed=100)
+        assert axisgen.epoch_is_nonzero(shapes, axisgen.WINDOWS[window][2])
+        k0, t0 = shapes[0]
+        first = axisgen.first_keyed_ts(k0, t0)
+        live = t0[(k0 != axisgen.NONE) & (t0 > axisgen.T0)]
+        assert live.min() < first < live.max()  # records of batch 0 on both sides of the first one
+        assert shapes[2][1].max() < live.min() < shapes[1][1].max()
+        st = _cross(spec, axisgen.with_columns(shapes, spec.col_types, 100))
+        assert len(st) > 0
+
+
+@pytest.mark.parametrize("first", [axisgen.T0, 5])
+def test_axis_span_points(first):
+    """The reference has no span limit: the four points around the op's
+    2^32-window span are ordinary records to both restatements."""
+    spec = OpSpec(abi.HSG_TUMBLING, abi.HSG_EMIT_PER_BATCH, size_ms=1, col_types=[abi.HSG_I64],
+                  aggs=ALL_AGG_SETS["full_i64"])
+    accepted, refused = axisgen.span_points(first)
+    batches = [(np.zeros(1, np.uint32), np.array([t], np.int64), [np.array([3], np.int64)], None)
+               for t in [first] + accepted + refused]
+    st = _cross(spec, batches, wms=[-1] * len(batches))
+    assert [s[1] for s in st] == sorted([first] + accepted + refused)
+
+
+@pytest.mark.parametrize("kind", ["tumbling", "hopping"])
+@pytest.mark.parametrize("adv", axisgen.ADVANCES, ids=lambda a: f"adv{a}")
+def test_axis_window_starts(adv, kind):
+    """Window starts near 0, 2^31, 2^32, 2^53 and 2^62 for every advance of
+    the GPU test: both restatements, and Python's own integers."""
+    size = adv if kind == "tumbling" else 2 * adv + 1
+    for anchor in axisgen.ANCHORS:
+        key, ts, grace = axisgen.window_start_batch(adv, size, anchor)
+        spec = OpSpec(abi.HSG_TUMBLING if kind == "tumbling" else abi.HSG_HOPPING, abi.HSG_EMIT_PER_BATCH,
+                      size_ms=size, advance_ms=adv, grace_ms=grace, aggs=[(abi.HSG_COUNT_ALL, 0)])
+        st = _cross(spec, [(key, ts, [], None)])
+        want = {}
+        for t in ts.tolist():
+            if t < 0:
+                continue
+            s = max(0, t - size + adv) // adv * adv
+            while s <= t:
+                want[s] = want.get(s, 0) + 1
+                s += adv
+        assert [(s[1], s[2], s[3][0]) for s in st] == [(s, s + size, c) for s, c in sorted(want.items())]
+        assert sum(want.values()) == axisgen.window_pairs(key, ts, size, adv)
+
+
+@pytest.mark.parametrize("emit", [abi.HSG_EMIT_PER_BATCH, abi.HSG_EMIT_PER_RECORD], ids=["batch", "changes"])
+@pytest.mark.parametrize("window", sorted(axisgen.WINDOWS))
+def test_axis_top(window, emit):
+    """Up to INT64_MAX - 1: window end + grace wraps (Int64) and the record is
+    dropped for that window, in both restatements alike; the batch wholly
+    above the wrap leaves no row."""
+    kind, kw = axisgen.window_kw(window)
+    _k, size, adv = axisgen.WINDOWS[window]
+    spec = OpSpec(kind, emit, col_types=[abi.HSG_I64], aggs=ALL_AGG_SETS["full_i64"], grace_ms=5_000, **kw)
+    shapes = axisgen.top_of_axis(size, adv, 5_000, n=150)
+    _cross(spec, axisgen.with_columns(shapes, spec.col_types, 3))
+    o = pyoracle.OracleOp(spec)
+    wm = -1
+    rows = []
+    for key, ts, cols, valid in axisgen.with_columns(shapes, spec.col_types, 3):
+        wm = o.push(key, ts, cols, valid, watermark=wm)
+        rows.append(len(o.drain()))
+    assert rows[0] > 0 and rows[1] > 0 and rows[2] > 0 and rows[3] == 0, rows
+    assert np.all(o.dump_state().win_end > 0)  # no accepted window's end wrapped
+    o.close()
+
+
+@pytest.mark.parametrize("gap", [0, 700])
+@pytest.mark.parametrize("base", sorted(axisgen.SESSION_BASES))
+def test_axis_sessions(base, gap):
+    spec = OpSpec(abi.HSG_SESSION, abi.HSG_EMIT_PER_RECORD, gap_ms=gap, col_types=[abi.HSG_I64, abi.HSG_F64],
+                  aggs=ALL_AGG_SETS["mixed"])
+    batches = axisgen.session_batches(axisgen.SESSION_BASES[base], spec.col_types, n=150)
+    assert all(abs(int(t)) + gap < 2**63 for b in batches for t in (b[1].min(), b[1].max()))
+    _cross(spec, batches)
 
 
 def test_faithful_and_fast_session_store_agree():

@@ -96,8 +96,21 @@ HSG_W_BETWEEN = 12
 HSG_W_AND = 13
 HSG_W_OR = 14
 HSG_W_NOT = 15
+HSG_W_FN = 32  # value -> value: the numeric function `arg` (hsg_fn); 16..31 are not opcodes
 HSG_WHERE_MAX_INS = 64
 HSG_WHERE_MAX_DEPTH = 8
+
+# hsg_fn: the reference's numeric unary functions (unaryOpOnValue, Internal/Codegen.hs:139-179)
+HSG_FN_NAMES = ["SIN", "SINH", "ASIN", "ASINH", "COS", "COSH", "ACOS", "ACOSH", "TAN", "TANH", "ATAN", "ATANH",
+                "ABS", "CEIL", "FLOOR", "ROUND", "SQRT", "SIGN", "LOG", "LOG2", "LOG10", "EXP"]
+(HSG_FN_SIN, HSG_FN_SINH, HSG_FN_ASIN, HSG_FN_ASINH, HSG_FN_COS, HSG_FN_COSH, HSG_FN_ACOS, HSG_FN_ACOSH,
+ HSG_FN_TAN, HSG_FN_TANH, HSG_FN_ATAN, HSG_FN_ATANH, HSG_FN_ABS, HSG_FN_CEIL, HSG_FN_FLOOR, HSG_FN_ROUND,
+ HSG_FN_SQRT, HSG_FN_SIGN, HSG_FN_LOG, HSG_FN_LOG2, HSG_FN_LOG10, HSG_FN_EXP) = range(22)
+HSG_FN_COUNT = 22
+# the exact family (function class 1); every other function is class 2
+HSG_FN_EXACT = (HSG_FN_ABS, HSG_FN_CEIL, HSG_FN_FLOOR, HSG_FN_ROUND, HSG_FN_SQRT, HSG_FN_SIGN)
+# ... whose result has the operand's type / is an i64; the rest give an f64
+HSG_FN_KEEP_TYPE = (HSG_FN_ABS, HSG_FN_CEIL, HSG_FN_FLOOR, HSG_FN_ROUND)
 
 
 class hsg_where_imm(C.Union):
@@ -110,9 +123,10 @@ class hsg_where_ins(C.Structure):
 
 def where_ins(op, arg=0):
     """One instruction: where_ins(HSG_W_COL, c), where_ins(HSG_W_I64, int),
-    where_ins(HSG_W_F64, float), where_ins(HSG_W_ADD) ..."""
+    where_ins(HSG_W_F64, float), where_ins(HSG_W_FN, HSG_FN_ABS),
+    where_ins(HSG_W_ADD) ..."""
     ins = hsg_where_ins(op=int(op), arg=0)
-    if op == HSG_W_COL:
+    if op == HSG_W_COL or op == HSG_W_FN:
         ins.arg = int(arg)
     elif op == HSG_W_I64:
         ins.imm.i = int(arg)
@@ -165,14 +179,25 @@ def _map_expr(e):
 
 
 def map_expr_type(e, col_types):
-    """The static type of a map expression: HSG_F64 iff an f64 column or
-    constant takes part (include/hstream_gpu.h)."""
+    """The static type of a (well-formed) map expression, as hsg_map_check
+    types it: ADD / SUB / MUL give an f64 iff an operand is one; of the
+    functions SIGN gives an i64, ABS / CEIL / FLOOR / ROUND the operand's
+    type, every other an f64 (include/hstream_gpu.h)."""
     prog, _ = _map_expr(e)
+    st = []
     for p in prog:
         op, arg = (p.op, p.arg) if isinstance(p, hsg_where_ins) else (p[0], p[1] if len(p) > 1 else 0)
-        if op == HSG_W_F64 or (op == HSG_W_COL and 0 <= arg < len(col_types) and col_types[arg] == HSG_F64):
-            return HSG_F64
-    return HSG_I64
+        if op == HSG_W_COL:
+            st.append(0 <= arg < len(col_types) and col_types[arg] == HSG_F64)
+        elif op in (HSG_W_I64, HSG_W_F64):
+            st.append(op == HSG_W_F64)
+        elif op == HSG_W_FN:
+            x = st.pop() if st else False
+            st.append(x if arg in HSG_FN_KEEP_TYPE else arg != HSG_FN_SIGN)
+        else:
+            r, l = (st.pop() if st else False), (st.pop() if st else False)
+            st.append(l or r)
+    return HSG_F64 if st and st[-1] else HSG_I64
 
 
 def map_array(exprs):
@@ -335,6 +360,8 @@ EXPORTED_SYMBOLS = [
     "hsg_op_create_mapped",
     "hsg_op_map_stats",
     "hsg_map_grid_threads",
+    "hsg_prog_fn_class",
+    "hsg_map_grid_threads_fn",
     "hsg_op_destroy",
     "hsg_op_reset",
     "hsg_last_error",

@@ -179,6 +179,69 @@ static int validate_config(const hsg_op_config *c, std::string &err, int32_t agg
 
 namespace hsg {
 
+static bool fn_exact(int32_t fn) {
+  return fn == HSG_FN_ABS || fn == HSG_FN_CEIL || fn == HSG_FN_FLOOR || fn == HSG_FN_ROUND || fn == HSG_FN_SIGN ||
+         fn == HSG_FN_SQRT;
+}
+
+int prog_fn_class(const hsg_where_ins *prog, int32_t n) {
+  int fc = 0;
+  for (int pc = 0; prog && pc < n; ++pc)
+    if (prog[pc].op == HSG_W_FN) fc = std::max(fc, fn_exact(prog[pc].arg) ? 1 : 2);
+  return fc;
+}
+
+// The static typing of one value instruction -- COL, I64, F64, ADD, SUB, MUL,
+// FN -- as the device carries it (hsg_pred.h), written once for the three
+// checkers: the values it pops (the top `pops` entries of is_f64[0 .. depth)
+// are its operands), with f64 the type of the value it pushes; -1: `in` is no
+// value instruction; -2: a fault, its text in msg. With fewer than `pops`
+// entries f64 is not set: the caller reports the underflow.
+static int value_ins_type(const hsg_where_ins &in, const int32_t *col_types, int32_t n_cols, const bool *is_f64,
+                          int depth, bool &f64, std::string &msg) {
+  f64 = false;
+  int pops = 0;
+  switch (in.op) {
+    case HSG_W_COL:
+      if (in.arg < 0 || in.arg >= n_cols) {
+        msg = "column " + std::to_string(in.arg) + " out of range";
+        return -2;
+      }
+      if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64) {
+        msg = "bad column type";
+        return -2;
+      }
+      f64 = col_types[in.arg] == HSG_F64;
+      return 0;
+    case HSG_W_I64: return 0;
+    case HSG_W_F64:
+      if (!(in.imm.f - in.imm.f == 0.0)) {
+        msg = "f64 constant is not finite";
+        return -2;
+      }
+      f64 = true;
+      return 0;
+    case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
+    case HSG_W_FN:
+      if (in.arg < 0 || in.arg >= HSG_FN_COUNT) {
+        msg = "bad function " + std::to_string(in.arg);
+        return -2;
+      }
+      pops = 1;
+      break;
+    default: return -1;
+  }
+  if (depth < pops) return pops;
+  // value value -> value: i64 only when both are
+  for (int k = 0; k < pops; ++k) f64 |= is_f64[depth - 1 - k];
+  if (in.op == HSG_W_FN) {
+    // ABS / CEIL / FLOOR / ROUND keep the operand's type, SIGN is an i64, the rest f64
+    if (in.arg == HSG_FN_SIGN) f64 = false;
+    else if (in.arg != HSG_FN_ABS && in.arg != HSG_FN_CEIL && in.arg != HSG_FN_FLOOR && in.arg != HSG_FN_ROUND) f64 = true;
+  }
+  return pops;
+}
+
 // (`what`: "where" over the value columns, "having" over the aggregate outputs)
 static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_t n, const int32_t *col_types,
                       int32_t n_cols, int32_t max_cols, std::string &err) {
@@ -197,20 +260,11 @@ static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_
     const hsg_where_ins &in = prog[pc];
     int pops = 0, want = K_VALUE, gives = K_VALUE;
     bool f64 = false;
-    switch (in.op) {
-      case HSG_W_COL:
-        if (in.arg < 0 || in.arg >= n_cols)
-          return fail(err, HSG_E_INVALID, at(pc) + "column " + std::to_string(in.arg) + " out of range");
-        if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64)
-          return fail(err, HSG_E_INVALID, at(pc) + "bad column type");
-        f64 = col_types[in.arg] == HSG_F64;
-        break;
-      case HSG_W_I64: break;
-      case HSG_W_F64:
-        if (!(in.imm.f - in.imm.f == 0.0)) return fail(err, HSG_E_INVALID, at(pc) + "f64 constant is not finite");
-        f64 = true;
-        break;
-      case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
+    std::string msg;
+    const int vp = value_ins_type(in, col_types, n_cols, is_f64, depth, f64, msg);
+    if (vp == -2) return fail(err, HSG_E_INVALID, at(pc) + msg);
+    if (vp >= 0) pops = vp;
+    else switch (in.op) {
       case HSG_W_EQ: case HSG_W_NE: case HSG_W_LT: case HSG_W_GT: case HSG_W_LE: case HSG_W_GE:
         pops = 2, gives = K_BOOL;
         break;
@@ -224,8 +278,6 @@ static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_
       if (kind[depth - 1 - k] != want)
         return fail(err, HSG_E_INVALID,
                     at(pc) + (want == K_VALUE ? "a bool used as a value" : "a value used as a bool"));
-    // value value -> value: i64 only when both are
-    for (int k = 0; k < pops && gives == K_VALUE; ++k) f64 |= is_f64[depth - 1 - k];
     depth -= pops;
     if (depth >= HSG_WHERE_MAX_DEPTH)
       return fail(err, HSG_E_INVALID, at(pc) + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
@@ -266,6 +318,7 @@ int having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg,
 void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, WhereProg &out) {
   memset(&out, 0, sizeof(out));
   out.n = n;
+  out.fn_class = (uint32_t)prog_fn_class(prog, n);
   for (int c = 0; c < n_cols; ++c)
     if (col_types[c] == HSG_F64) out.f64 |= 1u << c;
   for (int pc = 0; pc < n; ++pc) {
@@ -301,27 +354,13 @@ int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_typ
     for (int pc = 0; pc < x.n; ++pc) {
       const hsg_where_ins &in = x.prog[pc];
       const std::string at = what + "instruction " + std::to_string(pc) + ": ";
-      int pops = 0;
       bool f64 = false;
-      switch (in.op) {
-        case HSG_W_COL:
-          if (in.arg < 0 || in.arg >= n_cols)
-            return fail(err, HSG_E_INVALID, at + "column " + std::to_string(in.arg) + " out of range");
-          if (col_types[in.arg] != HSG_I64 && col_types[in.arg] != HSG_F64)
-            return fail(err, HSG_E_INVALID, at + "bad column type");
-          f64 = col_types[in.arg] == HSG_F64;
-          break;
-        case HSG_W_I64: break;
-        case HSG_W_F64:
-          if (!(in.imm.f - in.imm.f == 0.0)) return fail(err, HSG_E_INVALID, at + "f64 constant is not finite");
-          f64 = true;
-          break;
-        case HSG_W_ADD: case HSG_W_SUB: case HSG_W_MUL: pops = 2; break;
-        default:
-          return fail(err, HSG_E_INVALID, at + "opcode " + std::to_string(in.op) + " is not a value instruction");
-      }
+      std::string msg;
+      const int pops = value_ins_type(in, col_types, n_cols, is_f64, depth, f64, msg);
+      if (pops == -2) return fail(err, HSG_E_INVALID, at + msg);
+      if (pops == -1)
+        return fail(err, HSG_E_INVALID, at + "opcode " + std::to_string(in.op) + " is not a value instruction");
       if (depth < pops) return fail(err, HSG_E_INVALID, at + "stack underflow");
-      for (int k = 0; k < pops; ++k) f64 |= is_f64[depth - 1 - k];
       depth -= pops;
       if (depth >= HSG_WHERE_MAX_DEPTH)
         return fail(err, HSG_E_INVALID, at + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
@@ -332,6 +371,24 @@ int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_typ
     if (out_types) out_types[j] = is_f64[0] ? HSG_F64 : HSG_I64;
   }
   return HSG_OK;
+}
+
+// An expression (checked) holds a function that can give the error value or a
+// literal-form bit of its own (MapPlan::fn_valid): any but ABS / CEIL / FLOOR
+// / ROUND / SIGN of an i64, which is total and clears or keeps the bit.
+static bool fn_needs_valid(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols) {
+  bool is_f64[HSG_WHERE_MAX_DEPTH];
+  int depth = 0;
+  for (int pc = 0; pc < n; ++pc) {
+    bool f64 = false;
+    std::string msg;
+    const bool operand_f64 = depth > 0 && is_f64[depth - 1];
+    const int pops = value_ins_type(prog[pc], col_types, n_cols, is_f64, depth, f64, msg);
+    if (prog[pc].op == HSG_W_FN && (operand_f64 || prog[pc].arg == HSG_FN_SQRT || !fn_exact(prog[pc].arg))) return true;
+    depth -= pops;
+    is_f64[depth++] = f64;
+  }
+  return false;
 }
 
 void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, bool forms,
@@ -345,6 +402,7 @@ void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_
     if (col_types[c] == HSG_F64) out.f64 |= 1u << c;
   plan.n_exprs = n_exprs;
   plan.keys = where.n != 0;
+  plan.fn_class = where.n ? (int32_t)where.fn_class : 0;
   for (int j = 0; j < n_exprs; ++j) {
     const hsg_map_expr &x = exprs[j];
     const bool strict = (x.flags & HSG_MAP_STRICT) != 0;
@@ -357,6 +415,8 @@ void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_
       if (in.op == HSG_W_COL) plan.reads[j] |= 1u << in.arg;
       if (in.op == HSG_W_F64 && in.imm.f != __builtin_trunc(in.imm.f)) plan.const_form[j] = true;
     }
+    plan.fn_class = std::max(plan.fn_class, (int32_t)prog_fn_class(x.prog, x.n));
+    plan.fn_valid[j] = fn_needs_valid(x.prog, x.n, col_types, n_cols);
     if (alias && !strict) continue;  // the caller's column as it is: nothing to run
     for (int pc = 0; pc < x.n; ++pc) {
       hsg_where_ins in = x.prog[pc];
@@ -1179,6 +1239,10 @@ extern "C" int hsg_op_map_stats(const hsg_op *op, hsg_map_stats *out) {
 }
 
 extern "C" int hsg_map_grid_threads(void) { return hsg::kMapGrid * hsg::kMapThreads; }
+extern "C" int hsg_map_grid_threads_fn(int fn_class) {
+  return fn_class < 0 || fn_class > 2 ? 0 : hsg::map_grid(fn_class) * hsg::kMapThreads;
+}
+extern "C" int hsg_prog_fn_class(const hsg_where_ins *prog, int32_t n) { return hsg::prog_fn_class(prog, n); }
 
 namespace hsg {
 // For the sink encoder (sink.cpp): the op's device and which changelog

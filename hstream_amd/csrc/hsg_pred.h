@@ -11,6 +11,12 @@
 // eight named entries shifted on push / pop -- constant indices only, so it
 // stays in vector registers (no scratch) -- and the three-valued logic is a
 // per-lane error bit beside each entry.
+//
+// Everything here is templated on the kernel's function class FC (hsg_where.h
+// prog_fn_class): 0 has no HSG_W_FN branch, 1 the exact family, 2 all 22
+// functions. Each kernel is instantiated per class and the host launches the
+// class of the op's program, because a branch of the interpreter costs its
+// registers whether or not it is taken.
 #pragma once
 
 #include "hsg_where.h"
@@ -80,12 +86,86 @@ __device__ __forceinline__ int cmp_vals(uint64_t a, bool af, uint64_t b, bool bf
   return c == 2 ? 2 : -c;
 }
 
-// The value half of the instruction set -- COL, I64, F64, ADD, SUB, MUL -- on
-// the stack: cv[c] is the 8-byte word of column c (read for the columns the
-// program names only), bit c of `absent` says the column is the error value
-// for this row, bit c of `cform` is its literal-form bit, bit c of `f64` its
-// type. False: `in` is none of these (the stack is untouched).
-template <int NC>
+// HSG_W_FN on the top of the stack: the numeric function `fn` (hsg_fn, uniform
+// like the opcode), include/hstream_gpu.h and DESIGN.md 9 for the rules. FC is
+// the kernel's function class: 1 holds the exact family (ABS, CEIL, FLOOR,
+// ROUND, SIGN, SQRT), 2 all 22; the host launches the class of the op's
+// programs, so a class-1 kernel never meets another function. Every f64 result
+// passes through `+ 0.0`: a Scientific has no negative zero.
+template <int FC>
+__device__ __forceinline__ void fn_step(Stack &st, int32_t fn) {
+  const uint64_t x = st.v[0];
+  const bool xf = st.f & 1u;
+  const double xd = xf ? as_f64(x) : (double)(int64_t)x;  // toRealFloat
+  // the error value: the operand is, or it is an f64 that is not finite
+  bool e = (st.err & 1u) || (xf && !(xd - xd == 0.0));
+  bool fm = st.form & 1u;
+  bool of = xf;
+  uint64_t o = x;
+  if (fn == HSG_FN_ABS) {
+    // (the form bit stays: abs keeps a Scientific's exponent)
+    o = xf ? as_u64(__builtin_fabs(xd)) : ((int64_t)x < 0 ? 0ull - x : x);
+  } else if (fn == HSG_FN_CEIL || fn == HSG_FN_FLOOR || fn == HSG_FN_ROUND) {
+    // an i64 is its own ceiling; an f64 stays an f64 (exact for every double)
+    if (xf) {
+      const double r = fn == HSG_FN_CEIL ? __builtin_ceil(xd) : (fn == HSG_FN_FLOOR ? __builtin_floor(xd) : __builtin_rint(xd));
+      o = as_u64(r + 0.0);
+    }
+    fm = false;
+  } else if (fn == HSG_FN_SIGN) {
+    const bool pos = xf ? xd > 0.0 : (int64_t)x > 0, neg = xf ? xd < 0.0 : (int64_t)x < 0;
+    o = (uint64_t)((int64_t)pos - (int64_t)neg);
+    of = false;
+    fm = false;
+  } else {
+    // the f64 functions. The domain tests read the converted operand: (double)
+    // is monotonic and exact at -1, 0 and 1, so an i64 tests as the integer it is
+    double r = 0.0;
+    bool dom = false;
+    if (fn == HSG_FN_SQRT) {
+      dom = xd < 0.0;
+      r = ::sqrt(xd);
+    }
+    if constexpr (FC >= 2) {
+      switch (fn) {
+        case HSG_FN_SIN: r = ::sin(xd); break;
+        case HSG_FN_SINH: r = ::sinh(xd); break;
+        case HSG_FN_ASIN: dom = xd < -1.0 || xd > 1.0; r = ::asin(xd); break;
+        case HSG_FN_ASINH: r = ::asinh(xd); break;
+        case HSG_FN_COS: r = ::cos(xd); break;
+        case HSG_FN_COSH: r = ::cosh(xd); break;
+        case HSG_FN_ACOS: dom = xd < -1.0 || xd > 1.0; r = ::acos(xd); break;
+        case HSG_FN_ACOSH: dom = xd < 1.0; r = ::acosh(xd); break;
+        case HSG_FN_TAN: r = ::tan(xd); break;
+        case HSG_FN_TANH: r = ::tanh(xd); break;
+        case HSG_FN_ATAN: r = ::atan(xd); break;
+        case HSG_FN_ATANH: dom = xd <= -1.0 || xd >= 1.0; r = ::atanh(xd); break;
+        // LOG2 / LOG10 as the reference divides (Internal/Codegen.hs:173-178): the doubles log(2.0), log(10.0)
+        case HSG_FN_LOG: dom = xd <= 0.0; r = ::log(xd); break;
+        case HSG_FN_LOG2: dom = xd <= 0.0; r = ::log(xd) / 0.6931471805599453; break;
+        case HSG_FN_LOG10: dom = xd <= 0.0; r = ::log(xd) / 2.302585092994046; break;
+        case HSG_FN_EXP: r = ::exp(xd); break;
+        default: break;
+      }
+    }
+    r += 0.0;
+    e = e || dom || !(r - r == 0.0);
+    o = as_u64(r);
+    of = true;
+    fm = r != __builtin_trunc(r);  // fromFloatDigits of an integral double has no negative exponent
+  }
+  st.pop();
+  st.push(o, e, of, fm);
+}
+
+// The value half of the instruction set -- COL, I64, F64, ADD, SUB, MUL, and in
+// a kernel of function class FC > 0 also FN -- on the stack: cv[c] is the
+// 8-byte word of column c (read for the columns the program names only), bit
+// c of `absent` says the column is the error value for this row, bit c of
+// `cform` is its literal-form bit, bit c of `f64` its type. False: `in` is
+// none of these (the stack is untouched). FC = 0 has no FN branch at all: a
+// branch costs its registers taken or not.
+template <int FC, int NC>
 __device__ __forceinline__ bool value_step(Stack &st, const hsg_where_ins &in, uint32_t f64, const uint64_t (&cv)[NC],
                                            uint32_t absent, uint32_t cform) {
   const int32_t op = in.op;
@@ -114,6 +194,8 @@ __device__ __forceinline__ bool value_step(Stack &st, const hsg_where_ins &in, u
     st.pop();
     st.pop();
     st.push(o, e, lf || rf, fm);
+  } else if (FC > 0 && op == HSG_W_FN) {
+    if constexpr (FC > 0) fn_step<FC>(st, in.arg);
   } else {
     return false;
   }
@@ -122,13 +204,13 @@ __device__ __forceinline__ bool value_step(Stack &st, const hsg_where_ins &in, u
 
 // One row through the program (cv, absent: value_step). True = the row is
 // kept (the result is true, not false and not the error).
-template <int NC>
+template <int FC, int NC>
 __device__ __forceinline__ bool eval(const WhereProg &p, const uint64_t (&cv)[NC], uint32_t absent) {
   Stack st;
   st.clear();
   for (int pc = 0; pc < p.n; ++pc) {
     const int32_t op = p.ins[pc].op;
-    if (value_step(st, p.ins[pc], p.f64, cv, absent, 0u)) {
+    if (value_step<FC>(st, p.ins[pc], p.f64, cv, absent, 0u)) {
     } else if (op <= HSG_W_GE) {
       // value value -> bool; error if either operand is
       const int c = cmp_vals(st.v[1], (st.f >> 1) & 1u, st.v[0], st.f & 1u);

@@ -24,7 +24,7 @@ struct WhereProg {
   int32_t n;                           // 0 = the op has no WHERE
   uint32_t cols;                       // bit c: the program names column c
   uint32_t f64;                        // bit c: column c is HSG_F64
-  uint32_t reserved;
+  uint32_t fn_class;                   // host only: the kernel the program runs on (prog_fn_class)
   hsg_where_ins ins[HSG_WHERE_MAX_INS];
 };
 
@@ -42,7 +42,16 @@ int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, 
 // (checked program) -> WhereProg
 void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, WhereProg &out);
 
-void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a);
+// The function class of a program (hsg_prog_fn_class): 0 no HSG_W_FN, 1 the
+// exact family only (ABS, CEIL, FLOOR, ROUND, SIGN, SQRT), 2 any other.
+int prog_fn_class(const hsg_where_ins *prog, int32_t n);
+
+// workgroups per CU of one resident round of k_where<1> / k_where<2>, from
+// their reported occupancy: class 1 fits 7 and takes 6 as class
+// 0 does (k_where.hip launch_where), class 2 fits 2
+constexpr int kWhereGroupsFn1 = 6;
+constexpr int kWhereGroupsFn2 = 2;
+void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a, int fn_class);
 
 // ---- computed columns (k_map.hip) ---------------------------------------------
 // The op's map (include/hstream_gpu.h hsg_map_expr) as the pass runs it: the
@@ -55,6 +64,12 @@ constexpr int kMapThreads = 256;
 // the kernel's reported occupancy
 constexpr int kMapGroupsPerCU = 7;
 constexpr int kMapGrid = 256 * kMapGroupsPerCU;
+// ... of k_map<1> / k_map<2>, the function classes, from theirs
+constexpr int kMapGroupsFn1 = 7;
+constexpr int kMapGroupsFn2 = 2;
+constexpr int map_grid(int fn_class) {
+  return fn_class == 0 ? kMapGrid : 256 * (fn_class == 1 ? kMapGroupsFn1 : kMapGroupsFn2);
+}
 
 struct MapProg {
   WhereProg where;                     // where.n == 0: no filter; where.cols / f64 as k_where reads them
@@ -91,7 +106,11 @@ struct MapPlan {
   int32_t ocol[HSG_MAP_MAX_EXPRS] = {};   // ... or output ocol[j] of the pass
   uint32_t reads[HSG_MAP_MAX_EXPRS] = {}; // the columns expression j names
   bool const_form[HSG_MAP_MAX_EXPRS] = {};// expression j holds a constant whose literal-form bit is 1
+  // expression j holds a function that can give the error value or a literal-
+  // form bit of its own: any but ABS / CEIL / FLOOR / ROUND / SIGN of an i64
+  bool fn_valid[HSG_MAP_MAX_EXPRS] = {};
   bool keys = false;                      // the pass writes keys (a WHERE program or a strict expression)
+  int32_t fn_class = 0;                   // the kernel the pass runs: the maximum over WHERE and the expressions
 };
 
 // Type-check a map (hsg_map_check): HSG_OK with out_types (may be null), or HSG_E_INVALID with err set.
@@ -100,7 +119,7 @@ int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_typ
 // (checked map; `where` compiled or n == 0) -> MapProg + MapPlan
 void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, bool forms,
                  const WhereProg &where, MapProg &out, MapPlan &plan);
-void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a);
+void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a, int fn_class);
 
 // ---- HAVING pushdown (k_having.hip) ------------------------------------------
 // The same program over an op's changelog rows: column c is aggregate c of the
@@ -153,6 +172,9 @@ void having_types(const hsg_op_config *cfg, int32_t *types);
 
 // words of HavingArgs::state for a segment of up to `rows` rows
 inline uint64_t having_state_words(uint64_t rows) { return ((rows / kHavingTile + 1 + 2) + 1) & ~1ull; }
-void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a);
+// workgroups per CU of one resident round of k_having<1> / k_having<2> (class 0: 3, by LDS)
+constexpr int kHavingGroupsFn1 = 3;
+constexpr int kHavingGroupsFn2 = 2;
+void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a, int fn_class);
 
 }  // namespace hsg

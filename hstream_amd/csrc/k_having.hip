@@ -101,6 +101,8 @@ __device__ __forceinline__ uint64_t look_back(const uint64_t *tiles, uint64_t t,
 
 }  // namespace
 
+// FC: the function class of the program (hsg_pred.h), one kernel each
+template <int FC>
 __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArgs a) {
   __shared__ uint64_t s_w[3 + kMaxAggs][T];  // ws, we, src, aggregates
   __shared__ uint32_t s_key[T], s_form[T];
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
       const double d = pred::as_f64(cv[c]);
       if (((p.cols & p.f64) >> c) & 1u) absent |= d != d ? 1u << c : 0u;
     }
-    const bool keep = in && pred::eval(p, cv, absent);
+    const bool keep = in && pred::eval<FC>(p, cv, absent);
 
     // rank among the tile's kept rows
     const uint64_t m = __ballot(keep);
@@ -217,14 +219,18 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
   }
 }
 
-void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a) {
+void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a, int fn_class) {
   if (!p.n || !a.max_rows) return;
   // a workgroup per tile of the host's bound, at most one resident round (three
   // workgroups per CU by LDS); the workgroups take tiles until none is left, so
   // the grid bounds nothing but the parallelism
   uint64_t g = (a.max_rows + T - 1) / T;
-  if (g > 768) g = 768;
-  hipLaunchKernelGGL(k_having, dim3((unsigned)g), dim3(T), 0, s, p, a);
+  // (the function classes: a round of their own occupancy)
+  const uint64_t cap = 256 * (uint64_t)(fn_class == 0 ? 3 : (fn_class == 1 ? kHavingGroupsFn1 : kHavingGroupsFn2));
+  if (g > cap) g = cap;
+  if (fn_class == 0) hipLaunchKernelGGL(k_having<0>, dim3((unsigned)g), dim3(T), 0, s, p, a);
+  else if (fn_class == 1) hipLaunchKernelGGL(k_having<1>, dim3((unsigned)g), dim3(T), 0, s, p, a);
+  else hipLaunchKernelGGL(k_having<2>, dim3((unsigned)g), dim3(T), 0, s, p, a);
 }
 
 }  // namespace hsg

@@ -26,6 +26,8 @@
 
 namespace hsg {
 
+// FC: the function class of the op's programs (hsg_pred.h), one kernel each
+template <int FC>
 __global__ __launch_bounds__(kMapThreads) void k_map(const MapProg p, const MapArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kMapThreads;
   uint64_t w_dropped = 0, m_dropped = 0;
@@ -55,14 +57,14 @@ __global__ __launch_bounds__(kMapThreads) void k_map(const MapProg p, const MapA
       cform |= ((vb[c] >> 1) & 1u) << c;
     }
     if (!p.forms) cform = 0;
-    const bool keep = p.where.n ? pred::eval(p.where, cv, absent) : true;
+    const bool keep = p.where.n ? pred::eval<FC>(p.where, cv, absent) : true;
     // the expressions, one run after the other on one stack
     pred::Stack st;
     st.clear();
     bool strict_err = false;
     int r = 0;
     for (int pc = 0; pc < p.n_ins; ++pc) {
-      pred::value_step(st, p.ins[pc], p.f64, cv, absent, cform);
+      pred::value_step<FC>(st, p.ins[pc], p.f64, cv, absent, cform);
       if (pc + 1 == p.end[r]) {
         // the run's one value is the top of the stack
         const bool e = st.err & 1u;
@@ -94,13 +96,16 @@ __global__ __launch_bounds__(kMapThreads) void k_map(const MapProg p, const MapA
   }
 }
 
-void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a) {
+void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a, int fn_class) {
   if (!a.n || (!p.n_ins && !p.where.n)) return;
   // one resident round of workgroups over the 256 CUs (kMapGroupsPerCU from
   // the kernel's occupancy); a larger batch strides
   uint64_t g = (a.n + kMapThreads - 1) / kMapThreads;
-  if (g > (uint64_t)kMapGrid) g = kMapGrid;
-  hipLaunchKernelGGL(k_map, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
+  const uint64_t cap = (uint64_t)map_grid(fn_class);
+  if (g > cap) g = cap;
+  if (fn_class == 0) hipLaunchKernelGGL(k_map<0>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
+  else if (fn_class == 1) hipLaunchKernelGGL(k_map<1>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
+  else hipLaunchKernelGGL(k_map<2>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
 }
 
 }  // namespace hsg

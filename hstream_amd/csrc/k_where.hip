@@ -21,6 +21,8 @@ namespace hsg {
 
 constexpr int kWhereThreads = 256;
 
+// FC: the function class of the program (hsg_pred.h), one kernel each
+template <int FC>
 __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, const WhereArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * kWhereThreads;
   uint64_t dropped = 0;
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, cons
         if (in && a.valid[c] && !(a.valid[c][i] & 1u)) absent |= 1u << c;
       }
     }
-    const bool keep = pred::eval(p, cv, absent);
+    const bool keep = pred::eval<FC>(p, cv, absent);
     const bool drop = key != HSG_KEY_NONE && !keep;
     if (in) a.out[i] = drop ? HSG_KEY_NONE : key;
     const uint64_t m = __ballot(drop);
@@ -52,14 +54,18 @@ __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, cons
   if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(a.dropped, (unsigned long long)dropped);
 }
 
-void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a) {
+void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a, int fn_class) {
   if (!a.n || !p.n) return;
   // one resident round of workgroups: 6 per CU of 256 CUs (the kernel fits 7,
   // 28 waves per CU; a grid past what is resident runs a second, mostly empty
   // round), which also keeps the per-wave atomics to a few thousand
   uint64_t g = (a.n + kWhereThreads - 1) / kWhereThreads;
-  if (g > 1536) g = 1536;
-  hipLaunchKernelGGL(k_where, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
+  // (the function classes: a round of their own occupancy)
+  const uint64_t cap = 256 * (uint64_t)(fn_class == 0 ? 6 : (fn_class == 1 ? kWhereGroupsFn1 : kWhereGroupsFn2));
+  if (g > cap) g = cap;
+  if (fn_class == 0) hipLaunchKernelGGL(k_where<0>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
+  else if (fn_class == 1) hipLaunchKernelGGL(k_where<1>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
+  else hipLaunchKernelGGL(k_where<2>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
 }
 
 }  // namespace hsg

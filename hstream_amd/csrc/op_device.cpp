@@ -586,7 +586,7 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
       w.valid[c] = kb.valid[c];
     }
     w.dropped = (unsigned long long *)&d.sc->scratch[kWhereWord];
-    launch_where(d.stream, d.where, w);
+    launch_where(d.stream, d.where, w, (int)d.where.fn_class);
     DTRY(hipGetLastError());
     kb.key = w.out;
   }
@@ -607,14 +607,15 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
 // them, never into a caller's array) only when the pass can drop a record;
 // the computed outputs and their valid bytes go to the op's own staging, the
 // valid bytes only where one could be other than 1: an input of the
-// expression has a valid array, or the op keeps literal forms and the
-// expression holds a constant that is not integral. The kernels' column j is
-// then expression j.
+// expression has a valid array, the op keeps literal forms and the
+// expression holds a constant that is not integral, or the expression holds a
+// function that can give the error value or a form bit (MapPlan::fn_valid).
+// The kernels' column j is then expression j.
 static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
   const MapPlan &m = d.map;
   bool need_valid[HSG_MAP_MAX_EXPRS] = {};
   for (int j = 0; j < m.n_exprs; ++j) {
-    need_valid[j] = d.forms && m.const_form[j];
+    need_valid[j] = (d.forms && m.const_form[j]) || m.fn_valid[j];
     for (int c = 0; c < d.user_cols; ++c) need_valid[j] |= ((m.reads[j] >> c) & 1u) && kb.valid[c];
   }
   if (kb.n) {
@@ -636,7 +637,7 @@ static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &er
       a.ovalid[m.ocol[j]] = need_valid[j] ? d.map_valid[m.ocol[j]] : nullptr;
     }
     a.dropped = (unsigned int *)&d.sc->scratch[kWhereWord];
-    launch_map(d.stream, d.map_prog, a);
+    launch_map(d.stream, d.map_prog, a, m.fn_class);
     DTRY(hipGetLastError());
     if (a.out) kb.key = a.out;
   }
@@ -854,7 +855,7 @@ static int having_pass(OpDevice &d, std::string &err) {
   h.hold_emit = d.hv.hold_emit ? 1 : 0;
   h.state = d.hv_state;
   h.sc = d.sc;
-  launch_having(d.stream, d.having, h);
+  launch_having(d.stream, d.having, h, (int)d.having.fn_class);
   DTRY(hipGetLastError());
   return HSG_OK;
 }

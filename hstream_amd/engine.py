@@ -60,6 +60,10 @@ def load_library(path=LIB_PATH):
     L.hsg_op_map_stats.restype = C.c_int
     L.hsg_map_grid_threads.argtypes = []
     L.hsg_map_grid_threads.restype = C.c_int
+    L.hsg_map_grid_threads_fn.argtypes = [C.c_int]
+    L.hsg_map_grid_threads_fn.restype = C.c_int
+    L.hsg_prog_fn_class.argtypes = [P(abi.hsg_where_ins), C.c_int32]
+    L.hsg_prog_fn_class.restype = C.c_int
     L.hsg_having_tile_rows.argtypes = []
     L.hsg_having_tile_rows.restype = C.c_int
     L.hsg_op_stats.argtypes = [vp, P(abi.hsg_stats)]
@@ -141,6 +145,18 @@ def map_check(exprs, col_types):
 def map_grid_threads() -> int:
     """Threads of one resident round of the map pass's grid (hsg_map_grid_threads)."""
     return load_library().hsg_map_grid_threads()
+
+
+def map_grid_threads_fn(fn_class: int) -> int:
+    """hsg_map_grid_threads of the map kernel of a function class (hsg_map_grid_threads_fn)."""
+    return load_library().hsg_map_grid_threads_fn(fn_class)
+
+
+def prog_fn_class(program) -> int:
+    """hsg_prog_fn_class (host only, no GPU): 0 no function, 1 the exact
+    family only, 2 any other function."""
+    prog, n = abi.where_array(program)
+    return load_library().hsg_prog_fn_class(prog, n)
 
 
 def having_tile_rows() -> int:

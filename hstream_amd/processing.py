@@ -163,6 +163,7 @@ class Expr:
 
     tree: Any
     float_fields: Tuple[str, ...] = ()
+    functions: bool = False   # push the tree's numeric unary functions down too (sql.compile_expr)
 
     def __str__(self):
         return self.tree.name
@@ -223,6 +224,7 @@ class Where:
 
     cond: Any
     float_fields: Sequence[str] = ()
+    functions: bool = False   # push the condition's numeric unary functions down too (sql.compile_where)
 
 
 @dataclass
@@ -235,6 +237,7 @@ class Having:
     that of the aggregate without it."""
 
     cond: Any
+    functions: bool = False   # push the condition's numeric unary functions down too (sql.compile_having)
 
 
 @dataclass
@@ -354,7 +357,7 @@ class Table:
                         fields.append((name, name in f.float_fields))
                         self.numeric.append(True)
             names = [x for x, _ in fields]
-            spec.map = [abi.MapExpr(sql.compile_expr(f.tree, names, key_field=grouped.key_field),
+            spec.map = [abi.MapExpr(sql.compile_expr(f.tree, names, key_field=grouped.key_field, functions=f.functions),
                                     abi.HSG_MAP_STRICT if st else 0) if isinstance(f, Expr)
                         else abi.MapExpr([(abi.HSG_W_COL, fields.index((f, fl)))]) for f, fl, st in acols]
         self.where = where
@@ -372,13 +375,13 @@ class Table:
                     names.append(f)
                     fields.append((f, f in where.float_fields))
                     self.numeric.append(True)
-            spec.where = sql.compile_where(where.cond, names, key_field=grouped.key_field)
+            spec.where = sql.compile_where(where.cond, names, key_field=grouped.key_field, functions=where.functions)
         self.having = having
         if having is not None:
             # the filter over the emitted rows runs in the op too
             # (hsg_op_create_filtered), over the aggregates by alias
             from . import sql
-            spec.having = sql.compile_having(having.cond, self.aggs)
+            spec.having = sql.compile_having(having.cond, self.aggs, functions=having.functions)
         self.fields = fields
         self._decoder = None
         spec.col_types = [abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in fields]

@@ -150,6 +150,57 @@ RSearchCond = Union[RCondOp, RCondAnd, RCondOr, RCondNot, RCondBetween]
 _COMP_OPS = {"RCompOpEQ": abi.HSG_W_EQ, "RCompOpNE": abi.HSG_W_NE, "RCompOpLT": abi.HSG_W_LT,
              "RCompOpGT": abi.HSG_W_GT, "RCompOpLEQ": abi.HSG_W_LE, "RCompOpGEQ": abi.HSG_W_GE}
 _BIN_OPS = {"OpAdd": abi.HSG_W_ADD, "OpSub": abi.HSG_W_SUB, "OpMul": abi.HSG_W_MUL}
+# the 22 numeric unary functions (unaryOpOnValue, Internal/Codegen.hs:139-179): "OpSin" ... "OpLog10"
+_FN_OPS = {"Op" + n.capitalize(): i for i, n in enumerate(abi.HSG_FN_NAMES)}
+_FLOAT_FNS = {
+    abi.HSG_FN_SIN: math.sin, abi.HSG_FN_SINH: math.sinh, abi.HSG_FN_ASIN: math.asin, abi.HSG_FN_ASINH: math.asinh,
+    abi.HSG_FN_COS: math.cos, abi.HSG_FN_COSH: math.cosh, abi.HSG_FN_ACOS: math.acos, abi.HSG_FN_ACOSH: math.acosh,
+    abi.HSG_FN_TAN: math.tan, abi.HSG_FN_TANH: math.tanh, abi.HSG_FN_ATAN: math.atan, abi.HSG_FN_ATANH: math.atanh,
+    abi.HSG_FN_SQRT: math.sqrt, abi.HSG_FN_LOG: math.log, abi.HSG_FN_EXP: math.exp,
+    # as the reference divides (Internal/Codegen.hs:173-178), not log2 / log10
+    abi.HSG_FN_LOG2: lambda x: math.log(x) / math.log(2.0),
+    abi.HSG_FN_LOG10: lambda x: math.log(x) / math.log(10.0),
+}
+
+
+class MathematicalError(ArithmeticError):
+    """unaryOpOnValue's "Mathematical error" (a domain error), and this
+    engine's rule for a result that is not finite: the expression is the
+    error value for the record, as for a missing field."""
+
+
+def unary_value(fn: int, x: Fraction) -> Fraction:
+    """unaryOpOnValue for the numeric function fn (abi.HSG_FN_*) of an exact
+    Number. ABS, CEIL, FLOOR, ROUND (half to even, Haskell's round) and SIGN
+    are exact; every other function is the double function of toRealFloat x.
+    MathematicalError where the reference throws -- ASIN / ACOS outside
+    [-1, 1], ACOSH below 1, ATANH outside (-1, 1), LOG* at or below 0 -- and,
+    where the reference would make a meaningless finite number of a NaN or an
+    infinity, for SQRT of a negative number and for an operand or a result
+    that is not finite as a double."""
+    if fn == abi.HSG_FN_ABS:
+        return abs(x)
+    if fn == abi.HSG_FN_CEIL:
+        return Fraction(math.ceil(x))
+    if fn == abi.HSG_FN_FLOOR:
+        return Fraction(math.floor(x))
+    if fn == abi.HSG_FN_ROUND:
+        return Fraction(round(x))
+    if fn == abi.HSG_FN_SIGN:
+        return Fraction((x > 0) - (x < 0))
+    if fn not in _FLOAT_FNS:
+        raise TypeError(f"bad function {fn}")
+    if (fn in (abi.HSG_FN_ASIN, abi.HSG_FN_ACOS) and not -1 <= x <= 1) or (fn == abi.HSG_FN_ACOSH and x < 1) or \
+            (fn == abi.HSG_FN_ATANH and not -1 < x < 1) or \
+            (fn in (abi.HSG_FN_LOG, abi.HSG_FN_LOG2, abi.HSG_FN_LOG10) and x <= 0) or (fn == abi.HSG_FN_SQRT and x < 0):
+        raise MathematicalError("Mathematical error")
+    try:
+        r = _FLOAT_FNS[fn](float(x))
+    except (OverflowError, ValueError):
+        raise MathematicalError("the result is not finite")
+    if not math.isfinite(r):
+        raise MathematicalError("the result is not finite")
+    return Fraction(r)
 
 
 def _is_number(v) -> bool:
@@ -164,8 +215,9 @@ def _field_name(e: RExprCol) -> str:
 def _expr_value(e, value):
     """genRExprValue over a JSON object: the Number as an exact Fraction (a
     Scientific); raises KeyError for a missing field (getFieldByName,
-    Internal/Codegen.hs:41-49) and TypeError for what binOpOnValue /
-    compareValue have no case for."""
+    Internal/Codegen.hs:41-49), MathematicalError where a unary function
+    does (unary_value) and TypeError for what binOpOnValue / compareValue /
+    unaryOpOnValue have no numeric case for."""
     if isinstance(e, RExprCol):
         name = _field_name(e)
         if name not in value:
@@ -186,6 +238,8 @@ def _expr_value(e, value):
             return a - b
         if e.op == "OpMul":
             return a * b
+    if isinstance(e, RExprUnaryOp) and e.op in _FN_OPS:
+        return unary_value(_FN_OPS[e.op], _expr_value(e.expr, value))
     raise TypeError(f"unsupported expression {e!r}")
 
 
@@ -242,9 +296,10 @@ def where_fields(cond) -> List[str]:
     return out
 
 
-def _emit_expr(e, fields, key_field, what, prog) -> int:
+def _emit_expr(e, fields, key_field, what, prog, functions=False) -> int:
     """Append the value expression e to prog (postfix); returns the stack
-    depth it needs. ValueError for what the program cannot say."""
+    depth it needs. ValueError for what the program cannot say; a unary
+    function is said (HSG_W_FN) only with functions=True."""
     if isinstance(e, RExprCol):
         name = _field_name(e)
         if key_field is not None and name == key_field:
@@ -270,22 +325,30 @@ def _emit_expr(e, fields, key_field, what, prog) -> int:
     if isinstance(e, RExprBinOp):
         if e.op not in _BIN_OPS:
             raise ValueError(f"operator {e.op} is not pushed down")
-        d1 = _emit_expr(e.expr1, fields, key_field, what, prog)
-        d2 = _emit_expr(e.expr2, fields, key_field, what, prog)
+        d1 = _emit_expr(e.expr1, fields, key_field, what, prog, functions)
+        d2 = _emit_expr(e.expr2, fields, key_field, what, prog, functions)
         prog.append((_BIN_OPS[e.op],))
         return max(d1, 1 + d2)
     if isinstance(e, RExprUnaryOp):
-        raise ValueError(f"unary function {e.op} is not pushed down")
+        if not functions or e.op not in _FN_OPS:
+            raise ValueError(f"unary function {e.op} is not pushed down")
+        d = _emit_expr(e.expr, fields, key_field, what, prog, functions)
+        prog.append((abi.HSG_W_FN, _FN_OPS[e.op]))
+        return d
     raise ValueError(f"unsupported expression {e!r}")
 
 
-def compile_expr(e, fields: Sequence[str], key_field: Optional[str] = None, what: str = "SELECT") -> List[Tuple]:
-    """A value expression (RExprCol / RExprConst / RExprBinOp tree) as a
-    postfix value program, [(op,) | (op, arg)], over value columns named
-    `fields` (column c = fields[c]): one expression of the op's map. ValueError
-    for what the program cannot say, the same list as compile_where's."""
+def compile_expr(e, fields: Sequence[str], key_field: Optional[str] = None, what: str = "SELECT",
+                 functions: bool = False) -> List[Tuple]:
+    """A value expression (RExprCol / RExprConst / RExprBinOp / RExprUnaryOp
+    tree) as a postfix value program, [(op,) | (op, arg)], over value columns
+    named `fields` (column c = fields[c]): one expression of the op's map.
+    ValueError for what the program cannot say, the same list as
+    compile_where's. functions=True says the 22 numeric unary functions too
+    ((HSG_W_FN, HSG_FN_*) after the operand); off by default, because the
+    device's math library, not the host's, then rounds the float functions."""
     prog: List[Tuple] = []
-    depth = _emit_expr(e, list(fields), key_field, what, prog)
+    depth = _emit_expr(e, list(fields), key_field, what, prog, functions)
     if len(prog) > abi.HSG_MAP_MAX_INS:
         raise ValueError(f"{what} expression needs {len(prog)} instructions (max {abi.HSG_MAP_MAX_INS})")
     if depth > abi.HSG_WHERE_MAX_DEPTH:
@@ -295,28 +358,34 @@ def compile_expr(e, fields: Sequence[str], key_field: Optional[str] = None, what
 
 def expr_is_float(e, float_fields=()) -> bool:
     """The static type of a value expression: f64 iff a field that carries
-    decimals or a float constant takes part."""
+    decimals or a float constant takes part; of the unary functions SIGN is
+    an i64, ABS / CEIL / FLOOR / ROUND have their operand's type and every
+    other one is an f64."""
     if isinstance(e, RExprCol):
         return _field_name(e) in float_fields
     if isinstance(e, RExprConst):
         return isinstance(e.constant, float)
     if isinstance(e, RExprBinOp):
         return expr_is_float(e.expr1, float_fields) or expr_is_float(e.expr2, float_fields)
+    if isinstance(e, RExprUnaryOp) and e.op in _FN_OPS:
+        fn = _FN_OPS[e.op]
+        return expr_is_float(e.expr, float_fields) if fn in abi.HSG_FN_KEEP_TYPE else fn != abi.HSG_FN_SIGN
     return False
 
 
-def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, what: str = "WHERE") -> List[Tuple]:
+def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, what: str = "WHERE",
+                  functions: bool = False) -> List[Tuple]:
     """The condition as a postfix hsg_where_ins program, [(op,) | (op, arg)],
     over value columns named `fields` (column c = fields[c]). ValueError for
     what the program cannot say -- string / bool / null constants, a predicate
-    on the group key, the reference's unary functions, a non-finite constant, a
-    program past HSG_WHERE_MAX_INS or HSG_WHERE_MAX_DEPTH: such a WHERE stays
-    upstream of the op (genFilterNode)."""
+    on the group key, the reference's unary functions unless functions=True
+    (compile_expr), a non-finite constant, a program past HSG_WHERE_MAX_INS or
+    HSG_WHERE_MAX_DEPTH: such a WHERE stays upstream of the op (genFilterNode)."""
     fields = list(fields)
     prog: List[Tuple] = []
 
     def expr(e) -> int:
-        return _emit_expr(e, fields, key_field, what, prog)
+        return _emit_expr(e, fields, key_field, what, prog, functions)
 
     def search(c) -> int:
         if isinstance(c, RCondOp):
@@ -351,7 +420,7 @@ def compile_where(cond, fields: Sequence[str], key_field: Optional[str] = None, 
     return prog
 
 
-def compile_having(cond, aggs: Sequence) -> List[Tuple]:
+def compile_having(cond, aggs: Sequence, functions: bool = False) -> List[Tuple]:
     """The HAVING condition as the same postfix program over the op's
     aggregate outputs: column j is aggs[j] (P.Agg, or its alias), named by
     alias as the reference's filter reads the emitted object (genFilterR over
@@ -364,7 +433,7 @@ def compile_having(cond, aggs: Sequence) -> List[Tuple]:
     dup = sorted({a for a in aliases if aliases.count(a) > 1})
     if dup:
         raise ValueError(f"HAVING over duplicate aliases {dup} is not pushed down")
-    return compile_where(cond, aliases, what="HAVING")
+    return compile_where(cond, aliases, what="HAVING", functions=functions)
 
 
 # SELECT items: ("COUNT(*)",) / ("COUNT", col) / ("SUM", col) / ("MIN", col) /
@@ -373,7 +442,8 @@ def compile_having(cond, aggs: Sequence) -> List[Tuple]:
 SelItem = Tuple
 
 
-def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Optional[str] = None) -> List[P.Agg]:
+def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Optional[str] = None,
+                             functions: bool = False) -> List[P.Agg]:
     """genAggregateComponents (Codegen.hs:393-469). Where an item takes a
     column name it also takes a value expression (RExprBinOp / RExprConst /
     RExprCol tree): ("COL", expr) is genAggregateComponentsFromDerivedCol
@@ -382,7 +452,7 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Opt
     over an expression is this engine's, as AVG is, and skips such a record.
     The op's map pass evaluates the expression on the GPU. A tree that is just
     a column is the plain column. ValueError, and the query stays on the host,
-    for what compile_expr cannot say."""
+    for what compile_expr cannot say (functions: as compile_expr)."""
     out = []
     for item in sel:
         kind, *rest = item
@@ -402,10 +472,10 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Opt
             cname = col
         else:
             names = where_fields(col)
-            compile_expr(col, names, key_field)  # raises for what the program cannot say
+            compile_expr(col, names, key_field, functions=functions)  # raises for what the program cannot say
             fl = expr_is_float(col, float_fields)
             cname = col.name
-            col = P.Expr(col, tuple(f for f in names if f in float_fields))
+            col = P.Expr(col, tuple(f for f in names if f in float_fields), functions)
             strict = kind == "COL"
         if kind == "COUNT":
             out.append(P.COUNT(col, alias or f"COUNT({cname})"))
@@ -427,7 +497,7 @@ def gen_aggregate_components(sel: List[SelItem], float_fields=(), key_field: Opt
 
 
 def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.HSG_EMIT_PER_RECORD,
-                      float_fields=(), state_capacity=0, where=None, having=None) -> P.Table:
+                      float_fields=(), state_capacity=0, where=None, having=None, functions: bool = False) -> P.Table:
     """genGroupByNode: groupBy -> (timeWindowedBy | sessionWindowedBy)? -> aggregate.
     where: the query's RSearchCond, run by the op on the GPU where the
     reference chains genFilterNode in front (Codegen.hs:540); ValueError when
@@ -438,15 +508,17 @@ def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.H
     ValueError when compile_having cannot express it. As in the reference, it
     applies to an unwindowed GROUP BY only: for a windowed query (Codegen.hs:
     554-559 never looks at it) and for HSG_EMIT_NONE, which emits nothing, it
-    is dropped silently."""
+    is dropped silently. functions=True pushes the numeric unary functions of
+    the SELECT list, WHERE and HAVING down too (compile_expr); by default a
+    query that uses one raises ValueError and stays on the host."""
     grouped = P.groupBy(engine, group_by.column)
-    aggs = gen_aggregate_components(sel, float_fields, key_field=group_by.column)
+    aggs = gen_aggregate_components(sel, float_fields, key_field=group_by.column, functions=functions)
     mat = P.Materialized(state_capacity=state_capacity)
     if where is not None:
-        where = P.Where(where, float_fields)
+        where = P.Where(where, float_fields, functions)
     w = group_by.window
     if w is None:
-        hv = P.Having(having) if having is not None and emit != abi.HSG_EMIT_NONE else None
+        hv = P.Having(having, functions) if having is not None and emit != abi.HSG_EMIT_NONE else None
         return grouped.aggregate(aggs, mat, emit, where=where, having=hv)
     if isinstance(w, RTumblingWindow):
         return grouped.timeWindowedBy(P.mkTumblingWindow(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit,

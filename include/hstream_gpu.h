@@ -156,8 +156,31 @@ enum hsg_enc {
  * A record is kept only when the result is true. Both operands of AND / OR
  * are always computed (nothing has a side effect): the short circuit is a
  * rule on values. Not expressible, such a WHERE stays upstream of the op:
- * string / bool / null constants, predicates on the group key, the
- * reference's unary functions. */
+ * string / bool / null constants, predicates on the group key.
+ *
+ * FN (value -> value) applies the numeric function `arg` (hsg_fn), the
+ * reference's unaryOpOnValue (Internal/Codegen.hs:139-179). Typing is static:
+ *   ABS                  the operand's type; an i64 INT64_MIN wraps
+ *   CEIL / FLOOR / ROUND the operand's type: the identity on an i64, on an f64
+ *                        an f64 holding an integer; ROUND is half to even
+ *   SIGN                 i64: -1, 0 or 1
+ *   the other 17         f64; an i64 operand is converted with (double);
+ *                        LOG2 / LOG10 are log(x) / log(2.0), log(x) / log(10.0)
+ * The result is the error value (what an absent column is) when the operand
+ * is, and where the reference throws "Mathematical error": ASIN / ACOS outside
+ * [-1, 1], ACOSH below 1, ATANH outside (-1, 1), LOG / LOG2 / LOG10 at or
+ * below 0 (an i64 operand is tested as an integer). It is also the error
+ * value for SQRT of a negative number and for any function whose f64 operand
+ * or f64 result is not finite (the reference makes a meaningless finite number
+ * of those). */
+enum hsg_fn {
+  HSG_FN_SIN = 0, HSG_FN_SINH = 1, HSG_FN_ASIN = 2, HSG_FN_ASINH = 3,
+  HSG_FN_COS = 4, HSG_FN_COSH = 5, HSG_FN_ACOS = 6, HSG_FN_ACOSH = 7,
+  HSG_FN_TAN = 8, HSG_FN_TANH = 9, HSG_FN_ATAN = 10, HSG_FN_ATANH = 11,
+  HSG_FN_ABS = 12, HSG_FN_CEIL = 13, HSG_FN_FLOOR = 14, HSG_FN_ROUND = 15, HSG_FN_SQRT = 16, HSG_FN_SIGN = 17,
+  HSG_FN_LOG = 18, HSG_FN_LOG2 = 19, HSG_FN_LOG10 = 20, HSG_FN_EXP = 21
+};
+#define HSG_FN_COUNT 22
 enum hsg_where_opcode {
   HSG_W_COL = 0,  /* push value column `arg`                                  */
   HSG_W_I64 = 1,  /* push imm.i                                               */
@@ -165,7 +188,9 @@ enum hsg_where_opcode {
   HSG_W_ADD = 3, HSG_W_SUB = 4, HSG_W_MUL = 5,        /* value value -> value */
   HSG_W_EQ = 6, HSG_W_NE = 7, HSG_W_LT = 8, HSG_W_GT = 9, HSG_W_LE = 10, HSG_W_GE = 11, /* value value -> bool */
   HSG_W_BETWEEN = 12,                                  /* lo x hi -> bool      */
-  HSG_W_AND = 13, HSG_W_OR = 14, HSG_W_NOT = 15        /* bool (bool) -> bool  */
+  HSG_W_AND = 13, HSG_W_OR = 14, HSG_W_NOT = 15,       /* bool (bool) -> bool  */
+  /* 16..31 are not opcodes */
+  HSG_W_FN = 32                                        /* value -> value: hsg_fn `arg` */
 };
 typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } hsg_where_ins;
 #define HSG_WHERE_MAX_INS   64
@@ -208,8 +233,8 @@ typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } 
  * arithmetic, SUM(price * qty), are this engine's, as HSG_AVG is.
  *
  * A map is a list of value programs: hsg_where_ins sequences of HSG_W_COL,
- * HSG_W_I64, HSG_W_F64, HSG_W_ADD, HSG_W_SUB and HSG_W_MUL only, each leaving
- * exactly one value. COL arg names a column of the batch (cfg->n_cols,
+ * HSG_W_I64, HSG_W_F64, HSG_W_ADD, HSG_W_SUB, HSG_W_MUL and HSG_W_FN only, each
+ * leaving exactly one value. COL arg names a column of the batch (cfg->n_cols,
  * cfg->col_types), as in the WHERE program. Expression j defines the
  * aggregates' column j: with a map, cfg->aggs[].column indexes the
  * expressions, not the batch. An expression's type is static, i64 unless an
@@ -231,7 +256,9 @@ typedef struct { int32_t op; int32_t arg; union { int64_t i; double f; } imm; } 
  * the operands: COL gives the input's bit 1, an I64 constant 0, an F64
  * constant 1 iff it is not integral (2.0 is 2e0 to Scientific), ADD / SUB /
  * MUL the OR of their operands (DESIGN.md 9 for the one case this misses).
- * Without the flag bit 1 is 0.
+ * FN: ABS keeps its operand's bit, CEIL / FLOOR / ROUND / SIGN clear it, every
+ * other function sets it iff its result is not integral. Without the flag bit
+ * 1 is 0.
  *
  * WHERE comes first, over the raw columns, then the map: a record WHERE
  * dropped is not counted by the map. An expression that is a single COL is
@@ -454,7 +481,7 @@ int  hsg_having_tile_rows(void);
  * host code (no GPU). HSG_OK, with out_types[j] (may be null) the static type
  * of expression j, only when 1 <= n_exprs <= HSG_MAP_MAX_EXPRS, the programs
  * hold at most HSG_MAP_MAX_INS instructions together, every opcode is one of
- * COL / I64 / F64 / ADD / SUB / MUL, every program leaves exactly one value
+ * COL / I64 / F64 / ADD / SUB / MUL / FN, every program leaves exactly one value
  * and never holds more than HSG_WHERE_MAX_DEPTH, every column is in range and
  * every f64 constant is finite; else HSG_E_INVALID with a message in err that
  * begins "map: " ("map: expr <j>: " for a fault of expression j). */
@@ -478,6 +505,14 @@ int  hsg_op_map_stats(const hsg_op *op, hsg_map_stats *out);
 /* Threads of one resident round of the map pass's grid: a batch of more records
  * strides (tests size a batch past it). */
 int  hsg_map_grid_threads(void);
+/* The function class of a program; pure host code (no GPU): 0 = no HSG_W_FN,
+ * 1 = only ABS / CEIL / FLOOR / ROUND / SIGN / SQRT (the exact family), 2 =
+ * any other function. Each pass has one kernel per class, and an op runs the
+ * class of its programs: today's programs run today's kernels. */
+int  hsg_prog_fn_class(const hsg_where_ins *prog, int32_t n);
+/* hsg_map_grid_threads of the map pass's kernel of function class fn_class
+ * (0: hsg_map_grid_threads itself); 0 for a class that does not exist. */
+int  hsg_map_grid_threads_fn(int fn_class);
 void hsg_op_destroy(hsg_op *op);
 int  hsg_op_reset(hsg_op *op);            /* drop all state and pending rows          */
 const char *hsg_last_error(const hsg_op *op);

@@ -212,6 +212,33 @@ def map_array(exprs):
     return (hsg_map_expr * max(1, len(items)))(*items), len(items), keep
 
 
+class hsg_select_config(C.Structure):
+    """A select op (hsg_op_create_select): the batch's columns, the changelog's room, the flags."""
+
+    _fields_ = [
+        ("n_cols", C.c_int32),
+        ("flags", C.c_uint32),
+        ("col_types", C.POINTER(C.c_int32)),
+        ("out_capacity", C.c_uint64),
+    ]
+
+
+class hsg_select_stats(C.Structure):
+    _fields_ = [
+        ("where_dropped", C.c_uint64),
+        ("where_dropped_total", C.c_uint64),
+        ("expr_dropped", C.c_uint64),
+        ("expr_dropped_total", C.c_uint64),
+        ("having_dropped", C.c_uint64),
+        ("having_dropped_total", C.c_uint64),
+        ("emitted", C.c_uint64),
+        ("emitted_total", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class hsg_engine_config(C.Structure):
     _fields_ = [
         ("device", C.c_int32),
@@ -362,6 +389,11 @@ EXPORTED_SYMBOLS = [
     "hsg_map_grid_threads",
     "hsg_prog_fn_class",
     "hsg_map_grid_threads_fn",
+    "hsg_select_check",
+    "hsg_op_create_select",
+    "hsg_op_select_stats",
+    "hsg_select_tile_rows",
+    "hsg_select_grid_groups",
     "hsg_op_destroy",
     "hsg_op_reset",
     "hsg_last_error",

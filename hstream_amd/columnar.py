@@ -103,7 +103,8 @@ def make_batch(key_id, ts, cols=(), valid=None, mem=None, ts_base=None, col_enc=
     """Build an hsg_batch over numpy arrays (host) or torch tensors (device).
 
     Returns (hsg_batch, keepalive). Arrays must be contiguous: key_id uint32 /
-    int32, ts int64, cols int64 or float64, valid uint8 (or None = all present).
+    int32 (None for a select op's batch without keys: every record is live), ts
+    int64, cols int64 or float64, valid uint8 (or None = all present).
     Narrow transport (include/hstream_gpu.h hsg_enc): a uint16 key_id = ids sent
     as HSG_ENC_K16 (no HSG_KEY_NONE in the batch); ts_base given = ts holds
     int32 offsets from it (HSG_ENC_TS32); ts_frames given = ts holds uint16
@@ -116,8 +117,9 @@ def make_batch(key_id, ts, cols=(), valid=None, mem=None, ts_base=None, col_enc=
     col_enc = list(col_enc or [abi.HSG_ENC_FULL] * len(cols))
     keep = [key_id, ts]
     if not _is_torch(ts):
-        key_id = np.asarray(key_id)
-        key_id = np.ascontiguousarray(key_id, dtype=np.uint16 if key_id.dtype == np.uint16 else np.uint32)
+        if key_id is not None:
+            key_id = np.asarray(key_id)
+            key_id = np.ascontiguousarray(key_id, dtype=np.uint16 if key_id.dtype == np.uint16 else np.uint32)
         ts = np.ascontiguousarray(ts, dtype=np.int32 if ts_base is not None else
                                   np.uint16 if ts_frames is not None else np.int64)
         if ts_frames is not None:
@@ -148,7 +150,7 @@ def make_batch(key_id, ts, cols=(), valid=None, mem=None, ts_base=None, col_enc=
         cols=C.cast(col_ptrs, C.POINTER(C.c_void_p)),
         valid=C.cast(valid_ptrs, C.POINTER(C.c_void_p)) if valid_ptrs is not None else None,
     )
-    if str(key_id.dtype) in ("uint16", "torch.int16", "torch.uint16"):
+    if key_id is not None and str(key_id.dtype) in ("uint16", "torch.int16", "torch.uint16"):
         b.key_enc = abi.HSG_ENC_K16  # (HSG_ENC_K16: ids < 65536, no HSG_KEY_NONE)
     if ts_base is not None:
         b.ts_enc = abi.HSG_ENC_TS32

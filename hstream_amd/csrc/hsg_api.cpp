@@ -433,6 +433,56 @@ void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_
   }
 }
 
+// ---- scalar SELECT: the three programs of a select op ---------------------------
+int select_check(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
+                 const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols,
+                 int32_t *out_types, std::string &err) {
+  if (n_cols < 0 || n_cols > kMaxCols || (n_cols > 0 && !col_types))
+    return fail(err, HSG_E_INVALID, "select: bad value columns (max " + std::to_string(kMaxCols) + ")");
+  for (int c = 0; c < n_cols; ++c)
+    if (col_types[c] != HSG_I64 && col_types[c] != HSG_F64) return fail(err, HSG_E_INVALID, "select: bad column type");
+  if (n_where < 0 || n_having < 0) return fail(err, HSG_E_INVALID, "select: negative program length");
+  int rc = n_where ? where_check(where, n_where, col_types, n_cols, err) : HSG_OK;
+  if (rc != HSG_OK) return rc;
+  int32_t types[HSG_MAP_MAX_EXPRS] = {};
+  // (no expression at all is SELECT *: the rows carry src_index only)
+  if (n_exprs != 0) rc = map_check(exprs, n_exprs, col_types, n_cols, types, err);
+  if (rc != HSG_OK) return rc;
+  if (n_having) rc = prog_check("having", having, n_having, types, n_exprs, HSG_MAP_MAX_EXPRS, err);
+  if (rc != HSG_OK) return rc;
+  for (int j = 0; out_types && j < n_exprs; ++j) out_types[j] = types[j];
+  return HSG_OK;
+}
+
+int select_compile(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
+                   const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols, bool forms,
+                   SelectProg &out) {
+  memset(&out, 0, sizeof(out));
+  WhereProg wp;
+  memset(&wp, 0, sizeof(wp));
+  if (n_where) where_compile(where, n_where, col_types, n_cols, wp);
+  // every expression strict: map_compile then keeps each one, aliases included, as a run of its own
+  hsg_map_expr strict[HSG_MAP_MAX_EXPRS];
+  for (int j = 0; j < n_exprs; ++j) {
+    strict[j] = exprs[j];
+    strict[j].flags = HSG_MAP_STRICT;
+  }
+  MapPlan plan;
+  map_compile(strict, n_exprs, col_types, n_cols, forms, wp, out.m, plan);
+  int32_t types[HSG_MAP_MAX_EXPRS] = {};
+  std::string ignored;
+  if (n_exprs) map_check(exprs, n_exprs, col_types, n_cols, types, ignored);
+  out.n_exprs = n_exprs;
+  for (int j = 0; j < n_exprs; ++j)
+    if (types[j] == HSG_F64) out.ef64 |= 1u << j;
+  int fc = plan.fn_class;
+  if (n_having) {
+    where_compile(having, n_having, types, n_exprs, out.having);
+    fc = std::max(fc, (int)out.having.fn_class);
+  }
+  return fc;
+}
+
 }  // namespace hsg
 
 template <class F>
@@ -455,6 +505,16 @@ extern "C" int hsg_map_check(const hsg_map_expr *exprs, int32_t n_exprs, const i
                              int32_t *out_types, char *err, size_t err_len) {
   return checked_message(
       [&](std::string &msg) { return map_check(exprs, n_exprs, col_types, n_cols, out_types, msg); }, err, err_len);
+}
+
+extern "C" int hsg_select_check(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
+                                const hsg_where_ins *having, int32_t n_having, const int32_t *col_types,
+                                int32_t n_cols, char *err, size_t err_len) {
+  return checked_message(
+      [&](std::string &msg) {
+        return select_check(where, n_where, exprs, n_exprs, having, n_having, col_types, n_cols, nullptr, msg);
+      },
+      err, err_len);
 }
 
 extern "C" int hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, char *err,
@@ -622,6 +682,8 @@ struct hsg_op {
   uint64_t rec_base = 0;
   hsg_stats stats;
   hsg_map_stats map_stats = {};  // the map's counters (hsg_op_map_stats)
+  bool select = false;           // a select op (hsg_op_create_select): no group key, no state
+  hsg_select_stats sel_stats = {};
   // asynchronous pushes (hsg_push_batch_async): one completion thread per op
   std::mutex qmu;
   std::condition_variable qcv;
@@ -877,6 +939,70 @@ extern "C" int hsg_op_create_mapped(hsg_engine *eng, const hsg_op_config *cfg, c
   }
 }
 
+// A select op is an hsg_op with no aggregation behind it: to the calls that
+// take rows it is an op of n_exprs outputs (cfg.n_aggs), to the sink an op of
+// that many LAST columns, which print as its numbers do.
+extern "C" int hsg_op_create_select(hsg_engine *eng, const hsg_select_config *cfg, const hsg_where_ins *where,
+                                    int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
+                                    const hsg_where_ins *having, int32_t n_having, hsg_op **out) {
+  try {
+    if (!eng || !out) return HSG_E_INVALID;
+    *out = nullptr;
+    if (!cfg) return fail(eng->err, HSG_E_INVALID, "select: null config");
+    if (cfg->flags & ~HSG_OPF_LITERAL_FORMS) return fail(eng->err, HSG_E_INVALID, "select: bad flags");
+    int32_t types[HSG_MAP_MAX_EXPRS] = {};
+    int rc = select_check(where, n_where, exprs, n_exprs, having, n_having, cfg->col_types, cfg->n_cols, types, eng->err);
+    if (rc != HSG_OK) return rc;
+    hsg_op *op = new (std::nothrow) hsg_op();
+    if (!op) return HSG_E_OOM;
+    op->eng = eng;
+    op->select = true;
+    memset(&op->cfg, 0, sizeof(op->cfg));
+    op->cfg.window_kind = HSG_UNWINDOWED;
+    op->cfg.emit_mode = HSG_EMIT_PER_RECORD;
+    op->cfg.n_cols = cfg->n_cols;
+    op->cfg.n_aggs = n_exprs;
+    op->cfg.out_capacity = cfg->out_capacity;
+    op->cfg.flags = cfg->flags;
+    op->col_types.assign(cfg->col_types, cfg->col_types + cfg->n_cols);
+    op->user_cols = cfg->n_cols;
+    memset(&op->stats, 0, sizeof(op->stats));
+    memset(&op->prog, 0, sizeof(op->prog));
+    const bool forms = (cfg->flags & HSG_OPF_LITERAL_FORMS) != 0;
+    op->prog.n_out = n_exprs;
+    for (int j = 0; j < n_exprs; ++j) {
+      op->aggs.push_back(hsg_agg{HSG_LAST, j});
+      op->prog.out_kind[j] = types[j] == HSG_F64 ? O_F64 : O_I64;
+      op->prog.form_kind[j] = forms ? F_LAST : F_NONE;
+    }
+    OpDevice &d = op->dev;
+    d.is_select = true;
+    d.forms = forms;
+    d.sel_fc = select_compile(where, n_where, exprs, n_exprs, having, n_having, cfg->col_types, cfg->n_cols, forms, d.sel);
+    if (hipSetDevice(eng->device) != hipSuccess) { delete op; return HSG_E_DEVICE; }
+    // local on a sharded engine too: no communicator, each rank filters its own slice
+    rc = select_device_init(d, cfg->n_cols, cfg->col_types, n_exprs, eng->batch_cap, cfg->out_capacity, eng->err);
+    if (rc != HSG_OK) {
+      op_device_free(d);
+      delete op;
+      return rc;
+    }
+    *out = op;
+    return HSG_OK;
+  } catch (const std::bad_alloc &) {
+    return HSG_E_OOM;
+  } catch (...) {
+    return HSG_E_DEVICE;
+  }
+}
+
+extern "C" int hsg_op_select_stats(const hsg_op *op, hsg_select_stats *out) {
+  if (!op || !out || !op->select) return HSG_E_INVALID;
+  wait_idle(op);
+  *out = op->sel_stats;
+  return HSG_OK;
+}
+
 extern "C" int hsg_op_create_filtered(hsg_engine *eng, const hsg_op_config *cfg, const hsg_where_ins *where, int32_t n,
                                       const hsg_where_ins *having, int32_t n_having, hsg_op **out) {
   return hsg_op_create_mapped(eng, cfg, nullptr, 0, where, n, having, n_having, out);
@@ -935,7 +1061,8 @@ static int validate_batch(hsg_op *op, const hsg_batch *b, const int64_t *inout_w
   if (b->n_cols != op->user_cols) return fail(op->err, HSG_E_INVALID, "batch n_cols != op n_cols");
   if (b->mem != HSG_MEM_HOST && b->mem != HSG_MEM_DEVICE) return fail(op->err, HSG_E_INVALID, "bad batch mem");
   if (b->n > op->eng->batch_cap) return fail(op->err, HSG_E_CAPACITY, "batch larger than the engine's batch_capacity");
-  if (b->n && (!b->key_id || !b->ts)) return fail(op->err, HSG_E_INVALID, "null key_id / ts");
+  // (a select op's batch may come without keys: every record is live)
+  if (b->n && ((!b->key_id && !op->select) || !b->ts)) return fail(op->err, HSG_E_INVALID, "null key_id / ts");
   for (int c = 0; c < b->n_cols; ++c)
     if (b->n && (!b->cols || !b->cols[c])) return fail(op->err, HSG_E_INVALID, "null value column");
   // narrow transport (hsg_enc): ts as TS32 / TS16, i64 columns as I32, f64 columns as DEC32
@@ -995,6 +1122,17 @@ static int push_sync(hsg_op *op, const hsg_batch *b, int64_t *inout_watermark, i
       const uint64_t kept = op->dev.hv_kept < res.out_rows ? op->dev.hv_kept : res.out_rows;
       res.having_dropped = res.out_rows - kept;
       res.out_rows = kept;
+    }
+    if (op->select) {
+      hsg_select_stats &ss = op->sel_stats;
+      ss.where_dropped = op->dev.sel_dropped[0];
+      ss.expr_dropped = op->dev.sel_dropped[1];
+      ss.having_dropped = op->dev.sel_dropped[2];
+      ss.emitted = res.out_rows;
+      ss.where_dropped_total += ss.where_dropped;
+      ss.expr_dropped_total += ss.expr_dropped;
+      ss.having_dropped_total += ss.having_dropped;
+      ss.emitted_total += ss.emitted;
     }
     // state was mutated: account for what happened even on OOM / RANGE
     *inout_watermark = res.wm_out;
@@ -1160,6 +1298,7 @@ extern "C" int hsg_dump_state(hsg_op *op, hsg_rows *out, uint64_t *n_out) {
   try {
     if (!op || !n_out) return HSG_E_INVALID;
     wait_idle(op);
+    if (op->select) return fail(op->err, HSG_E_INVALID, "dump: a select op has no state");
     int rc = check_rows(op, out);
     if (rc != HSG_OK) return rc;
     *n_out = op->state_rows;
@@ -1178,6 +1317,7 @@ extern "C" int hsg_view_get(hsg_op *op, const uint32_t *key_ids, uint32_t n_keys
   try {
     if (!op || !n_out) return HSG_E_INVALID;
     wait_idle(op);
+    if (op->select) return fail(op->err, HSG_E_INVALID, "view_get: a select op has no state");
     int rc = check_rows(op, out);
     if (rc != HSG_OK) return rc;
     *n_out = 0;
@@ -1201,6 +1341,7 @@ extern "C" int hsg_table_join(hsg_op *table, const hsg_probe *probe, hsg_rows *o
     hsg_op *op = table;
     if (!op || !n_out) return HSG_E_INVALID;
     wait_idle(op);
+    if (op->select) return fail(op->err, HSG_E_INVALID, "table_join: a select op is no table");
     if (!probe) return fail(op->err, HSG_E_INVALID, "table_join: null probe");
     int rc = check_rows(op, out);
     if (rc != HSG_OK) return rc;
@@ -1264,6 +1405,11 @@ int op_sink_info(const hsg_op *op, int *device, int *n_aggs, uint32_t *f64_mask,
   *form_mask = fm;
   return HSG_OK;
 }
+}  // namespace hsg
+
+namespace hsg {
+// For the sink encoder (sink.cpp): a select op's source records carry no key.
+bool op_is_select(const hsg_op *op) { return op && op->select; }
 }  // namespace hsg
 
 namespace hsg {

@@ -9,6 +9,7 @@
 #include "hsg_internal.h"
 #include "hsg_part.h"
 #include "hsg_perrecord.h"
+#include "hsg_select.h"
 #include "hsg_where.h"
 
 namespace hsg {
@@ -119,6 +120,16 @@ struct OpDevice {
   uint64_t hv_state_words = 0;
   bool hv_ran = false;           // the last fetch of this push found the pass's word
   uint64_t hv_kept = 0;
+  // Scalar SELECT (k_select.hip): the op has no aggregation at all. op_push
+  // stages the batch as every op does and runs push_select: one launch, then
+  // the fetch of the scalars, which brings back the rows kept, the three drop
+  // counts and the batch's maximum ts (hsg_select.h kSel*Word).
+  bool is_select = false;
+  SelectProg sel = {};
+  int32_t sel_fc = 0;             // the kernel's function class: the maximum over the three programs
+  uint64_t *sel_state = nullptr;  // ticket and tile states (grow-only)
+  uint64_t sel_state_words = 0;
+  uint64_t sel_dropped[3] = {};   // the last push: WHERE, expression, HAVING
   uint64_t wpr = 1;             // max windows per record
   bool sql_lean = false;        // per-batch LAST / literal-form op on the SQL lean kernels (k_agg_sql.hip)
   bool sql_wide = false;        // ... at 3 - 8 columns or 17 - 24 slots (k_agg_sql_wide.hip; PartParams::sql_wide)
@@ -257,6 +268,11 @@ struct PushResult {
 
 int op_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &prog, uint64_t batch_cap, int nranks, bool sharded,
                    uint64_t wpr, std::string &err);
+// a select op's device side: stream, scalars, staging for n_cols columns and a
+// changelog of out_cap rows with n_exprs aggregate columns (d.is_select, d.sel,
+// d.forms set by the caller)
+int select_device_init(OpDevice &d, int n_cols, const int32_t *col_types, int n_exprs, uint64_t batch_cap,
+                       uint64_t out_cap, std::string &err);
 void op_device_free(OpDevice &d);
 int op_device_reset(OpDevice &d, const hsg_op_config &cfg, const Program &prog, std::string &err);
 int op_push(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const PushArgs &a, PushResult &r,

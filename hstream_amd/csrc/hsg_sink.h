@@ -15,6 +15,7 @@ constexpr int kSinkMaxMembers = 16;
 //   2 + M      }  (or {} when the value object has no member)
 struct SinkDev {
   int32_t windowed;
+  int32_t keyless;     // a select op's sink: every key record is empty and the key is never read
   int32_t n_members;
   const char *frag;
   uint32_t frag_off[2 + kSinkMaxMembers + 2];

@@ -675,6 +675,7 @@ struct hsg_keydict {
 // ---------------------------------------------------------------------------
 struct hsg_decoder {
   std::string key_field;
+  bool keyless = false;        // no key field (a select op's source): every decoded record gets key id 0
   bool literal_forms = false;  // valid bit 1: the number's literal has a negative exponent
   struct Col {
     std::string field;
@@ -724,7 +725,7 @@ int decode_one(const hsg_decoder &dec, const char *s, size_t n, uint64_t i, void
   int state[32];
   Num cnum[32];
   for (int c = 0; c < C; ++c) state[c] = 0;
-  bool have_key = false;
+  bool have_key = dec.keyless;
   const size_t key_at = ch.arena.size();
   cur.ws();
   if (!cur.eat('}')) {
@@ -738,7 +739,7 @@ int decode_one(const hsg_decoder &dec, const char *s, size_t n, uint64_t i, void
       if (!cur.eat(':')) return HSG_DEC_NOT_OBJECT;
       cur.ws();
       bool used = false;
-      if (name_is(ks, kn, kesc, dec.key_field, tmp)) {
+      if (!dec.keyless && name_is(ks, kn, kesc, dec.key_field, tmp)) {
         // the last occurrence wins (Aeson objects are maps)
         ch.arena.resize(key_at);
         if (spell) ch.forms.resize(form_at);
@@ -912,11 +913,12 @@ extern "C" int hsg_keydict_text(const hsg_keydict *d, uint32_t id, char *buf, si
 }
 
 extern "C" int hsg_decoder_create(const hsg_decoder_config *cfg, hsg_decoder **out) {
-  if (!cfg || !out || !cfg->key_field || cfg->n_cols < 0 || cfg->n_cols > 32) return HSG_E_INVALID;
+  if (!cfg || !out || cfg->n_cols < 0 || cfg->n_cols > 32) return HSG_E_INVALID;
   if (cfg->n_cols && (!cfg->col_fields || !cfg->col_types)) return HSG_E_INVALID;
   try {
     hsg_decoder *d = new hsg_decoder();
-    d->key_field = cfg->key_field;
+    d->keyless = !cfg->key_field;
+    if (cfg->key_field) d->key_field = cfg->key_field;
     d->literal_forms = cfg->literal_forms != 0;
     for (int c = 0; c < cfg->n_cols; ++c) {
       if (!cfg->col_fields[c] || (cfg->col_types[c] != HSG_I64 && cfg->col_types[c] != HSG_F64)) {
@@ -938,7 +940,7 @@ extern "C" int hsg_decode_json_spelled(hsg_decoder *dec, hsg_keydict *dict, uint
                                        const uint64_t *off, const int64_t *rec_ts, uint32_t *key_id, int64_t *ts,
                                        void *const *cols, uint8_t *const *valid, uint8_t *status, uint64_t *rejected,
                                        uint32_t *spell, int n_threads) {
-  if (!dec || !dict || (n && (!buf || !off || !key_id))) return HSG_E_INVALID;
+  if (!dec || (!dict && !dec->keyless) || (n && (!buf || !off || !key_id))) return HSG_E_INVALID;
   const int C = (int)dec->cols.size();
   if (C && (!cols || !valid)) return HSG_E_INVALID;
   for (int c = 0; c < C; ++c)
@@ -992,6 +994,12 @@ extern "C" int hsg_decode_json_spelled(hsg_decoder *dec, hsg_keydict *dict, uint
           if (spell) spell[i] = HSG_KEY_NONE;
           for (int c = 0; c < C; ++c) valid[c][i] = 0;
           ++rej;
+          continue;
+        }
+        if (dec->keyless) {
+          // no key to look up: the record is live, the dictionary is not touched
+          key_id[i] = 0;
+          if (spell) spell[i] = 0;
           continue;
         }
         const char *cb = ch.arena.data() + ch.koff[j];

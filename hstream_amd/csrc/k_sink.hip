@@ -75,11 +75,11 @@ template <bool FORMS>
 __global__ __launch_bounds__(256) void k_sink_len(SinkDev S, uint64_t n, uint32_t *__restrict__ klen,
                                                   uint32_t *__restrict__ vlen) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t k = row_key(S, i);
+    const uint32_t k = S.keyless ? HSG_KEY_NONE : row_key(S, i);
     const char *p;
-    uint32_t kn;
-    key_text(S, k, p, kn);
-    klen[i] = (S.windowed ? 16u : 0u) + frag_len(S, 0) + kn + frag_len(S, 1);
+    uint32_t kn = 0;
+    if (!S.keyless) key_text(S, k, p, kn);
+    klen[i] = S.keyless ? 0u : (S.windowed ? 16u : 0u) + frag_len(S, 0) + kn + frag_len(S, 1);
     uint32_t vn = frag_len(S, 2 + S.n_members);
     char buf[FORMS ? kNumTextIntMax : kNumTextMax];
     for (int m = 0; m < S.n_members; ++m) vn += frag_len(S, 2 + m) + member_text<FORMS>(S, m, i, k, buf, p);
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void k_sink_write(SinkDev S, uint64_t n, const
                                                     const uint64_t *__restrict__ voff, char *__restrict__ kbytes,
                                                     char *__restrict__ vbytes) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t k = row_key(S, i);
+    const uint32_t k = S.keyless ? HSG_KEY_NONE : row_key(S, i);
     char *o = kbytes + koff[i];
     if (S.windowed) {
       // timeWindowSerde: int64BE start ++ int64BE 0
@@ -111,11 +111,13 @@ __global__ __launch_bounds__(256) void k_sink_write(SinkDev S, uint64_t n, const
       o += 16;
     }
     const char *p;
-    uint32_t kn;
-    key_text(S, k, p, kn);
-    o = put_frag(o, S, 0);
-    o = put(o, p, kn);
-    put_frag(o, S, 1);
+    if (!S.keyless) {
+      uint32_t kn;
+      key_text(S, k, p, kn);
+      o = put_frag(o, S, 0);
+      o = put(o, p, kn);
+      put_frag(o, S, 1);
+    }
     char *v = vbytes + voff[i];
     char buf[FORMS ? kNumTextIntMax : kNumTextMax];
     for (int m = 0; m < S.n_members; ++m) {

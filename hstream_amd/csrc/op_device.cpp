@@ -221,7 +221,9 @@ int op_device_reset(OpDevice &d, const hsg_op_config &cfg, const Program &prog, 
   d.sc_clean = false;
   d.where_seen = 0;
   d.map_seen = 0;
-  if (cfg.window_kind == HSG_SESSION) {
+  if (d.is_select) {
+    // no state: the scalars and the pending rows (the caller's count) are all there is
+  } else if (cfg.window_kind == HSG_SESSION) {
     int rc = session_device_reset(d, err);
     if (rc != HSG_OK) return rc;
   } else {
@@ -381,6 +383,37 @@ int op_device_init(OpDevice &d, const hsg_op_config &cfg, const Program &prog, u
   return op_device_reset(d, cfg, prog, err);
 }
 
+int select_device_init(OpDevice &d, int n_cols, const int32_t *col_types, int n_exprs, uint64_t batch_cap,
+                       uint64_t out_cap, std::string &err) {
+  d.nranks = 1;
+  d.n_cols = n_cols;
+  d.user_cols = n_cols;
+  for (int c = 0; c < n_cols; ++c) d.col_types[c] = col_types[c];
+  d.wpr = 1;
+  d.batch_cap = batch_cap;
+  DTRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+  DTRY(hipEventCreate(&d.ev_a));
+  DTRY(hipEventCreate(&d.ev_b));
+  DTRY(hipEventCreateWithFlags(&d.ev_fetch, hipEventDisableTiming));
+  DTRY(dalloc(&d.sc, 1));
+  DTRY(hipHostMalloc((void **)&d.h_sc, sizeof(DevScalars), hipHostMallocDefault));
+  DTRY(dalloc(&d.st_key, d.batch_cap));
+  DTRY(dalloc(&d.st_ts, d.batch_cap));
+  for (int c = 0; c < n_cols; ++c) {
+    DTRY(dalloc(&d.st_col[c], d.batch_cap));
+    DTRY(dalloc(&d.st_valid[c], d.batch_cap));
+  }
+  d.out_cap = out_cap ? out_cap : batch_cap;
+  int rc = alloc_out(d.out, d.out_cap, n_exprs, err, d.forms);
+  d.own_out = d.out;
+  d.own_out_cap = d.out_cap;
+  if (rc != HSG_OK) return rc;
+  DTRY(hipMemsetAsync(d.sc, 0, sizeof(DevScalars), d.stream));
+  memset(d.h_sc, 0, sizeof(DevScalars));
+  DTRY(hipStreamSynchronize(d.stream));
+  return HSG_OK;
+}
+
 void op_device_free(OpDevice &d) {
   if (d.aux) hipStreamSynchronize(d.aux);
   if (d.stream) hipStreamSynchronize(d.stream);
@@ -442,6 +475,9 @@ void op_device_free(OpDevice &d) {
   if (d.hv_state) hipFree(d.hv_state);
   d.hv_state = nullptr;
   d.hv_state_words = 0;
+  if (d.sel_state) hipFree(d.sel_state);
+  d.sel_state = nullptr;
+  d.sel_state_words = 0;
   if (d.tj.mem) hipFree(d.tj.mem);
   d.tj.mem = nullptr;
   d.tj.cap = 0;
@@ -519,7 +555,7 @@ static int widen_batch(OpDevice &d, const hsg_batch *b, const void *k16, const v
   WidenArgs w;
   memset(&w, 0, sizeof(w));
   w.n = b->n;
-  if (b->key_enc == HSG_ENC_K16) {
+  if (b->key_enc == HSG_ENC_K16 && b->key_id) {
     w.k16 = (const uint16_t *)k16;
     w.key = d.st_key;
     kb.key = d.st_key;
@@ -682,7 +718,7 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
   if (b->mem == HSG_MEM_DEVICE) {
     // the producer's stream is not ordered with ours: wait on its event
     if (b->ready_event) DTRY(hipStreamWaitEvent(d.stream, (hipEvent_t)b->ready_event, 0));
-    kb.key = b->key_id;
+    kb.key = b->key_id;  // (null: a select op's batch without keys)
     kb.ts = b->ts;
     for (int c = 0; c < b->n_cols; ++c) {
       kb.col[c] = (const int64_t *)b->cols[c];
@@ -701,14 +737,14 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
     const hipMemcpyKind k = hipMemcpyHostToDevice;
     const void *c32[kMaxCols] = {};
     if (n) {
-      if (b->key_enc == HSG_ENC_K16) DTRY(hipMemcpyAsync(d.nar_key, b->key_id, n * 2, k, d.stream));
-      else DTRY(hipMemcpyAsync(d.st_key, b->key_id, n * 4, k, d.stream));
+      if (b->key_id && b->key_enc == HSG_ENC_K16) DTRY(hipMemcpyAsync(d.nar_key, b->key_id, n * 2, k, d.stream));
+      else if (b->key_id) DTRY(hipMemcpyAsync(d.st_key, b->key_id, n * 4, k, d.stream));
       if (b->ts_enc != HSG_ENC_FULL) DTRY(hipMemcpyAsync(d.nar_ts, b->ts, n * ts_bytes(b), k, d.stream));
       else DTRY(hipMemcpyAsync(d.st_ts, b->ts, n * 8, k, d.stream));
       if (b->ts_enc == HSG_ENC_TS16)
         DTRY(hipMemcpyAsync(ts16_frames_at(d.nar_ts, n), b->ts_frames, ts16_frames(n) * 8, k, d.stream));
     }
-    kb.key = d.st_key;
+    kb.key = b->key_id ? d.st_key : nullptr;
     kb.ts = d.st_ts;
     for (int c = 0; c < b->n_cols; ++c) {
       const bool nar = b->col_enc[c] != HSG_ENC_FULL;
@@ -723,10 +759,10 @@ static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::stri
     return widen_batch(d, b, d.nar_key, d.nar_ts, ts16_frames_at(d.nar_ts, n), c32, kb, err);
   }
   if (n) {
-    DTRY(hipMemcpyAsync(d.st_key, b->key_id, n * 4, hipMemcpyHostToDevice, d.stream));
+    if (b->key_id) DTRY(hipMemcpyAsync(d.st_key, b->key_id, n * 4, hipMemcpyHostToDevice, d.stream));
     DTRY(hipMemcpyAsync(d.st_ts, b->ts, n * 8, hipMemcpyHostToDevice, d.stream));
   }
-  kb.key = d.st_key;
+  kb.key = b->key_id ? d.st_key : nullptr;  // (null: a select op's batch without keys)
   kb.ts = d.st_ts;
   for (int c = 0; c < b->n_cols; ++c) {
     if (n) DTRY(hipMemcpyAsync(d.st_col[c], b->cols[c], n * 8, hipMemcpyHostToDevice, d.stream));
@@ -810,6 +846,10 @@ int clear_batch_scalars(OpDevice &d, std::string &err) {
 static int status_from_err(uint32_t e, std::string &err) {
   if (e & ERR_HAVING) {
     err = "having: the changelog filter did not complete (internal)";
+    return HSG_E_DEVICE;
+  }
+  if (e & ERR_SELECT) {
+    err = "select: the compaction did not complete (internal)";
     return HSG_E_DEVICE;
   }
   if (e & ERR_OOM) {
@@ -917,6 +957,70 @@ int finish_batch(OpDevice &d, int64_t wm_in, uint64_t n, PushResult &r, std::str
   r.touched = s.touched;
   r.state_rows = s.live + d.spilled_rows;
   return status_from_err(s.err, err);
+}
+
+// A select op's batch (hsg_select.h): one launch over the staged batch, then
+// the fetch every push ends with. The caller's room check holds pending + n
+// <= out_cap, so the kernel writes inside the changelog columns whatever it
+// keeps.
+static int push_select(OpDevice &d, const PushArgs &a, const Batch &kb, PushResult &r, std::string &err) {
+  int rc = clear_batch_scalars(d, err);
+  if (rc != HSG_OK) return rc;
+  if (kb.n) {
+    const uint64_t words = select_state_words(kb.n);
+    if (words > d.sel_state_words) {
+      if (d.sel_state) hipFree(d.sel_state);
+      d.sel_state = nullptr;
+      d.sel_state_words = 0;
+      const uint64_t want = words > 2 * 1024 ? 2 * words : 2 * 1024;
+      DTRY(hipMalloc((void **)&d.sel_state, want * sizeof(uint64_t)));
+      d.sel_state_words = want;
+    }
+    DTRY(hipMemsetAsync(d.sel_state, 0, words * sizeof(uint64_t), d.stream));
+    SelectArgs s;
+    memset(&s, 0, sizeof(s));
+    s.n = kb.n;
+    s.key = kb.key;
+    s.ts = kb.ts;
+    for (int c = 0; c < d.user_cols; ++c) {
+      s.col[c] = kb.col[c];
+      s.valid[c] = kb.valid[c];
+    }
+    s.out = d.out;
+    s.base = a.pending;
+    s.rec_base = a.rec_base;
+    s.state = d.sel_state;
+    s.sc = d.sc;
+    DTRY(hipEventRecord(d.ev_a, d.stream));
+    launch_select(d.stream, d.sel, s, d.sel_fc);
+    DTRY(hipGetLastError());
+    DTRY(hipEventRecord(d.ev_b, d.stream));
+  }
+  rc = fetch_scalars(d, err);
+  if (rc != HSG_OK) return rc;
+  const DevScalars &h = *d.h_sc;
+  rc = status_from_err(h.err, err);
+  if (rc != HSG_OK) return rc;
+  if (kb.n && !(h.scratch[kSelectWord] & kSelectRan)) {
+    err = "select: the pass left no row count (internal)";
+    return HSG_E_DEVICE;
+  }
+  r.out_rows = kb.n ? h.scratch[kSelectWord] & ~kSelectRan : 0;
+  d.sel_dropped[0] = h.scratch[kSelWhereWord];
+  d.sel_dropped[1] = h.scratch[kSelExprWord];
+  d.sel_dropped[2] = h.scratch[kSelHavingWord];
+  // stream time: the maximum ts of the batch, skipped records included
+  r.wm_out = a.wm_in;
+  if (h.scratch[kSelTsWord]) {
+    const int64_t top = (int64_t)(h.scratch[kSelTsWord] ^ (1ull << 63));
+    if (top > r.wm_out) r.wm_out = top;
+  }
+  if (kb.n) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, d.ev_a, d.ev_b) == hipSuccess) r.agg_ms = ms;
+    r.agg_launches = 1;
+  }
+  return HSG_OK;
 }
 
 static int push_time_atomic(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const PushArgs &a,
@@ -1212,6 +1316,19 @@ int op_push(OpDevice &d, const hsg_op_config &cfg, const Program &prog, const Pu
   const hsg_batch *b = a.batch;
   d.where_staged = nullptr;  // a new push: stage_batch filters it
   d.hv_ran = false;
+  if (d.is_select) {
+    // the changelog must have room for the batch's worst case: every record kept
+    if (a.pending + b->n > d.out_cap) {
+      err = "changelog buffer full: drain before pushing (out_capacity)";
+      return HSG_E_CAPACITY;
+    }
+    Batch kb;
+    int rc = stage_batch(d, b, kb, err, a.staged_set);
+    if (rc != HSG_OK) return rc;
+    r.owned = kb.n;
+    r.global_records = kb.n;
+    return push_select(d, a, kb, r, err);
+  }
   // room in the table for the batch's worst case (sharded ops: in push_local,
   // once the records this rank owns are known)
   if (!a.comm) {

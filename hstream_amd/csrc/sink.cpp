@@ -17,6 +17,7 @@
 namespace hsg {
 // hsg_api.cpp: the op's device and aggregate output types
 int op_sink_info(const hsg_op *op, int *device, int *n_aggs, uint32_t *f64_mask, uint32_t *form_mask, int8_t *ident);
+bool op_is_select(const hsg_op *op);
 // ingest.cpp: the dictionary's key texts (Aeson encoding), back to back, and
 // its alternate spellings
 void keydict_texts(const hsg_keydict *d, const char **text, const uint64_t **off, uint64_t *n);
@@ -235,8 +236,12 @@ void sink_member_order(const char *const *aliases, int n, int32_t *order) {
 }  // namespace hsg
 
 extern "C" int hsg_sink_create(hsg_op *op, const hsg_keydict *dict, const hsg_sink_config *cfg, hsg_sink **out) {
-  if (!op || !dict || !cfg || !out || !cfg->key_field || cfg->n_members < 0 || cfg->n_members > kSinkMaxMembers)
-    return HSG_E_INVALID;
+  if (!op || !cfg || !out || cfg->n_members < 0 || cfg->n_members > kSinkMaxMembers) return HSG_E_INVALID;
+  // A select op's sink has no key: the reference's source records carry none,
+  // so every key record is empty (key_field NULL; dict is then not read and
+  // no member can be the key). Every other op's sink names its key field.
+  const bool keyless = !cfg->key_field;
+  if (keyless != op_is_select(op) || (!keyless && !dict) || (keyless && cfg->windowed)) return HSG_E_INVALID;
   if (cfg->n_members && (!cfg->aliases || !cfg->agg_index)) return HSG_E_INVALID;
   *out = nullptr;
   hsg_sink *s = new (std::nothrow) hsg_sink();
@@ -249,7 +254,7 @@ extern "C" int hsg_sink_create(hsg_op *op, const hsg_keydict *dict, const hsg_si
     return rc;
   }
   for (int m = 0; m < cfg->n_members; ++m)
-    if (!cfg->aliases[m] || cfg->agg_index[m] < -1 || cfg->agg_index[m] >= s->n_aggs) {
+    if (!cfg->aliases[m] || cfg->agg_index[m] < (keyless ? 0 : -1) || cfg->agg_index[m] >= s->n_aggs) {
       delete s;
       return HSG_E_INVALID;
     }
@@ -261,9 +266,9 @@ extern "C" int hsg_sink_create(hsg_op *op, const hsg_keydict *dict, const hsg_si
     frag += t;
   };
   std::string kp = "{";
-  put_json_string(kp, cfg->key_field);
+  if (!keyless) put_json_string(kp, cfg->key_field);
   kp += ":";
-  add(kp);
+  add(kp);  // (unused by a keyless sink)
   add("}");
   // members in the HashMap's traversal order (sink_member_order)
   int32_t order[kSinkMaxMembers];
@@ -280,6 +285,7 @@ extern "C" int hsg_sink_create(hsg_op *op, const hsg_keydict *dict, const hsg_si
   fo.push_back((uint32_t)frag.size());
   for (size_t f = 0; f < fo.size(); ++f) s->S.frag_off[f] = fo[f];
   s->S.windowed = cfg->windowed ? 1 : 0;
+  s->S.keyless = keyless ? 1 : 0;
   s->S.n_members = cfg->n_members;
   s->S.f64_mask = f64;
   s->S.form_mask = fmask;
@@ -320,7 +326,7 @@ extern "C" int hsg_sink_encode_spelled(hsg_sink *s, const hsg_rows *rows, uint64
   if (rows->n_aggs != s->n_aggs || (rows->mem != HSG_MEM_HOST && rows->mem != HSG_MEM_DEVICE) ||
       (out->mem != HSG_MEM_HOST && out->mem != HSG_MEM_DEVICE))
     return HSG_E_INVALID;
-  if (n && (!rows->key_id || (s->S.windowed && !rows->win_start))) return HSG_E_INVALID;
+  if (n && ((!rows->key_id && !s->S.keyless) || (s->S.windowed && !rows->win_start))) return HSG_E_INVALID;
   bool need_agg[kMaxAggs] = {};
   for (int m = 0; m < s->S.n_members; ++m)
     if (s->S.agg_index[m] >= 0) {
@@ -330,8 +336,8 @@ extern "C" int hsg_sink_encode_spelled(hsg_sink *s, const hsg_rows *rows, uint64
   if (!out->key_off || !out->value_off) return HSG_E_INVALID;
   try {
     STRY(hipSetDevice(s->device));
-    int rc = sync_keys(s);
-    if (rc == HSG_OK) rc = sync_alts(s);
+    int rc = s->S.keyless ? HSG_OK : sync_keys(s);
+    if (rc == HSG_OK && !s->S.keyless) rc = sync_alts(s);
     if (rc != HSG_OK) return rc;
     hipStream_t st = s->stream;
     *key_need = *value_need = 0;
@@ -397,7 +403,7 @@ extern "C" int hsg_sink_encode_spelled(hsg_sink *s, const hsg_rows *rows, uint64
         }
         s->st_cap = c;
       }
-      STRY(hipMemcpyAsync(s->st_key, rows->key_id, n * 4, hipMemcpyHostToDevice, st));
+      if (!s->S.keyless) STRY(hipMemcpyAsync(s->st_key, rows->key_id, n * 4, hipMemcpyHostToDevice, st));
       if (s->S.windowed) STRY(hipMemcpyAsync(s->st_ws, rows->win_start, n * 8, hipMemcpyHostToDevice, st));
       for (int j = 0; j < s->n_aggs; ++j)
         if (need_agg[j]) STRY(hipMemcpyAsync(s->st_agg[j], rows->aggs[j], n * 8, hipMemcpyHostToDevice, st));

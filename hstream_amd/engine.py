@@ -62,6 +62,18 @@ def load_library(path=LIB_PATH):
     L.hsg_map_grid_threads.restype = C.c_int
     L.hsg_map_grid_threads_fn.argtypes = [C.c_int]
     L.hsg_map_grid_threads_fn.restype = C.c_int
+    L.hsg_select_check.argtypes = [P(abi.hsg_where_ins), C.c_int32, P(abi.hsg_map_expr), C.c_int32,
+                                   P(abi.hsg_where_ins), C.c_int32, P(C.c_int32), C.c_int32, C.c_char_p, C.c_size_t]
+    L.hsg_select_check.restype = C.c_int
+    L.hsg_op_create_select.argtypes = [vp, P(abi.hsg_select_config), P(abi.hsg_where_ins), C.c_int32,
+                                       P(abi.hsg_map_expr), C.c_int32, P(abi.hsg_where_ins), C.c_int32, P(vp)]
+    L.hsg_op_create_select.restype = C.c_int
+    L.hsg_op_select_stats.argtypes = [vp, P(abi.hsg_select_stats)]
+    L.hsg_op_select_stats.restype = C.c_int
+    L.hsg_select_tile_rows.argtypes = []
+    L.hsg_select_tile_rows.restype = C.c_int
+    L.hsg_select_grid_groups.argtypes = []
+    L.hsg_select_grid_groups.restype = C.c_int
     L.hsg_prog_fn_class.argtypes = [P(abi.hsg_where_ins), C.c_int32]
     L.hsg_prog_fn_class.restype = C.c_int
     L.hsg_having_tile_rows.argtypes = []
@@ -140,6 +152,30 @@ def map_check(exprs, col_types):
     buf = C.create_string_buffer(256)
     rc = L.hsg_map_check(arr, n, types, len(col_types), out, buf, len(buf))
     return rc, buf.value.decode(), list(out)[:n] if rc == abi.HSG_OK else None
+
+
+def select_check(col_types, exprs=(), where=None, having=None):
+    """hsg_select_check (host only, no GPU): (status, message) for the three
+    programs of a select op over value columns of the given types; where /
+    having None = none, exprs may be empty (SELECT *)."""
+    L = load_library()
+    wprog, wn = abi.where_array(where) if where is not None else (None, 0)
+    hprog, hn = abi.where_array(having) if having is not None else (None, 0)
+    arr, n, keep = abi.map_array(exprs)
+    types = (C.c_int32 * max(1, len(col_types)))(*col_types)
+    buf = C.create_string_buffer(256)
+    rc = L.hsg_select_check(wprog, wn, arr, n, hprog, hn, types, len(col_types), buf, len(buf))
+    return rc, buf.value.decode()
+
+
+def select_tile_rows() -> int:
+    """Records per tile of the select kernel (hsg_select_tile_rows)."""
+    return load_library().hsg_select_tile_rows()
+
+
+def select_grid_groups() -> int:
+    """Most workgroups one launch of the select kernel starts (hsg_select_grid_groups)."""
+    return load_library().hsg_select_grid_groups()
 
 
 def map_grid_threads() -> int:
@@ -224,6 +260,16 @@ class Engine:
     def op(self, spec: OpSpec) -> "GpuOp":
         return GpuOp(self, spec)
 
+    def select_op(self, col_types, exprs=(), where=None, having=None, out_capacity=0, flags=0) -> "GpuOp":
+        """hsg_op_create_select: the op without a group key. exprs are value
+        programs (abi.MapExpr or bare programs; none = SELECT *, the rows carry
+        src_index only), where / having programs or None. The rows' aggs[j] is
+        expression j."""
+        spec = OpSpec(abi.HSG_UNWINDOWED, abi.HSG_EMIT_PER_RECORD, col_types=list(col_types),
+                      aggs=[(abi.HSG_LAST, j) for j in range(len(exprs))], out_capacity=out_capacity, flags=flags,
+                      where=where, having=having, map=list(exprs))
+        return GpuOp(self, spec, select=True)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.hsg_engine_destroy(self._h)
@@ -242,11 +288,19 @@ P_u8 = C.POINTER(C.c_uint8)
 class GpuOp(OpHandle):
     """One windowed GROUP BY operator on the GPU (hsg_op_create)."""
 
-    def __init__(self, engine: Engine, spec: OpSpec):
+    def __init__(self, engine: Engine, spec: OpSpec, select=False):
         cfg, keep = spec.to_config()
         h = C.c_void_p()
         what = "hsg_op_create"
-        if spec.map:
+        if select:
+            what = "hsg_op_create_select"
+            scfg = abi.hsg_select_config(n_cols=cfg.n_cols, flags=spec.flags, col_types=cfg.col_types,
+                                         out_capacity=spec.out_capacity)
+            marr, mn, mkeep = abi.map_array(spec.map or ())
+            wprog, wn = abi.where_array(spec.where) if spec.where is not None else (None, 0)
+            hprog, hn = abi.where_array(spec.having) if spec.having is not None else (None, 0)
+            rc = engine._lib.hsg_op_create_select(engine._h, C.byref(scfg), wprog, wn, marr, mn, hprog, hn, C.byref(h))
+        elif spec.map:
             what = "hsg_op_create_mapped"
             marr, mn, mkeep = abi.map_array(spec.map)
             wprog, wn = abi.where_array(spec.where) if spec.where is not None else (None, 0)
@@ -360,6 +414,12 @@ class GpuOp(OpHandle):
                 continue
             self._check(rc, "table_join")
             return truncate(arrs, got)
+
+    def select_stats(self) -> dict:
+        """hsg_op_select_stats: a select op's drop and row counts."""
+        s = abi.hsg_select_stats()
+        self._check(self._lib.hsg_op_select_stats(self._h, C.byref(s)), "op_select_stats")
+        return s.as_dict()
 
     def map_stats(self) -> dict:
         """hsg_op_map_stats: the map's counters (zeros for an op without one)."""

@@ -150,7 +150,8 @@ class Decoder:
         self._fields = (C.c_char_p * max(1, n))(*[f.encode() for f, _, _ in self.cols])
         self._types = (C.c_int32 * max(1, n))(*[t for _, t, _ in self.cols])
         self._num = (C.c_uint8 * max(1, n))(*[1 if num else 0 for _, _, num in self.cols])
-        cfg = abi.hsg_decoder_config(key_field=key_field.encode(), n_cols=n, col_fields=self._fields,
+        # (key_field None: no key, every decoded record gets key id 0 -- a select op's source)
+        cfg = abi.hsg_decoder_config(key_field=key_field.encode() if key_field is not None else None, n_cols=n, col_fields=self._fields,
                                      col_types=self._types, col_numeric=self._num,
                                      literal_forms=1 if literal_forms else 0)
         h = C.c_void_p()
@@ -181,7 +182,7 @@ class Decoder:
                                                    C.byref(rej), spell.ctypes.data, int(threads)),
                    "hsg_decode_json_spelled")
             return key, ts_out, cols, valid, status, int(rej.value), spell
-        _check(self._L.hsg_decode_json(self._h, keys.handle, n, buf, off.ctypes.data, ts_in.ctypes.data,
+        _check(self._L.hsg_decode_json(self._h, keys.handle if keys is not None else None, n, buf, off.ctypes.data, ts_in.ctypes.data,
                                        key.ctypes.data, ts_out.ctypes.data, cp, vp, status.ctypes.data,
                                        C.byref(rej), int(threads)), "hsg_decode_json")
         return key, ts_out, cols, valid, status, int(rej.value)

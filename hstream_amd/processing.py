@@ -12,6 +12,8 @@ Names and argument meaning follow hstream-processing (Yu-zh/hstream):
                                                      SessionWindowedStream.hs:33-72
   Materialized                                       Stream/Internal.hs:123-128
   runTask (poll loop + stream time)                  Processor.hs:99-144
+  Stream.filter / Stream.map                         Stream.hs:151-194 (the scalar SELECT
+                                                     chain, Codegen.hs:542-550)
   time-window / session key serdes                   TimeWindows.hs:68-93,
                                                      hstream-sql/.../Codegen/Boilerplate.hs:60-88
 
@@ -474,6 +476,152 @@ class Table:
         self.op.close()
 
 
+class Stream:
+    """A stream without a group key: HS.filter / HS.map (Stream.hs:151-194) as
+    the SQL code generator chains them for a SELECT without GROUP BY
+    (genFilterNode -> genMapNode -> genFilteRNodeFromHaving, Codegen.hs:542-550),
+    backed by one select op (hsg_op_create_select), built on first use.
+
+      Stream(engine, fields).filter(Where).map(exprs).having(Having)
+
+    fields: the numeric fields the query reads, each a name or (name,
+    is_float), in the batch's column order. exprs: [(alias, tree)] with tree a
+    field name or an hstream_amd.sql value expression; without map() the stream
+    is SELECT *: the op returns indices and process() forwards the original
+    records. Every field must hold a Number where present (a present
+    non-number drops the record at ingest: the programs compute numbers only).
+
+    process(records) runs one poll batch and returns (stream time, the records
+    forwarded, in arrival order) as {"value": {alias: number}, "timestamp": ts}."""
+
+    def __init__(self, engine, fields: Sequence, literal_forms: bool = False, out_capacity: int = 0):
+        self.engine = engine
+        self.fields = [(f, False) if isinstance(f, str) else (f[0], bool(f[1])) for f in fields]
+        self.literal_forms = literal_forms
+        self.out_capacity = out_capacity
+        self.where_prog = None
+        self.having_prog = None
+        self.exprs: Optional[List[Tuple[str, List[Tuple]]]] = None  # None: SELECT *
+        self._having = None
+        self._op = None
+        self._decoder = None
+        self.last_rows: Optional[Rows] = None  # the rows the last process / process_json drained (for the sink)
+
+    def _names(self):
+        return [f for f, _ in self.fields]
+
+    def filter(self, where: Where) -> "Stream":
+        from . import sql
+        self.where_prog = sql.compile_where(where.cond, self._names(), functions=where.functions)
+        return self
+
+    def map(self, exprs: Sequence[Tuple[str, Any]], functions: bool = False) -> "Stream":
+        from . import sql
+        if len(exprs) > abi.HSG_MAP_MAX_EXPRS:
+            raise ValueError(f"SELECT list of {len(exprs)} expressions (max {abi.HSG_MAP_MAX_EXPRS})")
+        aliases = [a for a, _ in exprs]
+        dup = sorted({a for a in aliases if aliases.count(a) > 1})
+        if dup:
+            raise ValueError(f"SELECT list with duplicate aliases {dup} is not pushed down")
+        out = []
+        for alias, tree in exprs:
+            if isinstance(tree, Expr):
+                functions_here, tree = tree.functions or functions, tree.tree
+            else:
+                functions_here = functions
+            if isinstance(tree, str):
+                tree = sql.RExprCol(tree, None, tree)
+            out.append((alias, sql.compile_expr(tree, self._names(), functions=functions_here)))
+        if sum(len(p) for _, p in out) > abi.HSG_MAP_MAX_INS:
+            raise ValueError(f"SELECT list needs more than {abi.HSG_MAP_MAX_INS} instructions")
+        self.exprs = out
+        if self._having is not None:
+            self.having(self._having)
+        return self
+
+    def having(self, having: Having) -> "Stream":
+        from . import sql
+        self._having = having
+        self.having_prog = sql.compile_having(having.cond, [a for a, _ in (self.exprs or [])],
+                                              functions=having.functions)
+        return self
+
+    @property
+    def aliases(self) -> List[str]:
+        return [a for a, _ in (self.exprs or [])]
+
+    @property
+    def op(self):
+        if self._op is None:
+            self._op = self.engine.select_op(
+                [abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in self.fields], [p for _, p in (self.exprs or [])],
+                where=self.where_prog, having=self.having_prog, out_capacity=self.out_capacity,
+                flags=abi.HSG_OPF_LITERAL_FORMS if self.literal_forms else 0)
+        return self._op
+
+    def sink(self):
+        """The sink encoder of this stream's rows (hstream_amd.sink.Sink): no
+        key (every key record is empty), the value object {alias: value}."""
+        from .sink import Sink
+        return Sink(self.op, None, None, [(a, j) for j, a in enumerate(self.aliases)], windowed=False)
+
+    def columns(self, records):
+        n = len(records)
+        keys = np.zeros(n, dtype=np.uint32)
+        ts = np.empty(n, dtype=np.int64)
+        cols = [np.zeros(n, dtype=np.float64 if fl else np.int64) for _, fl in self.fields]
+        valid = [np.ones(n, dtype=np.uint8) for _ in self.fields]
+        for i, rec in enumerate(records):
+            value = rec["value"]
+            ts[i] = rec["timestamp"]
+            for c, (f, fl) in enumerate(self.fields):
+                if f not in value:
+                    valid[c][i] = 0
+                    continue
+                v = value[f]
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                    keys[i] = abi.HSG_KEY_NONE  # the programs compute numbers only
+                    break
+                cols[c][i] = float(v) if fl else int(v)
+        return keys, ts, cols, valid
+
+    def _forward(self, rows: Rows, base: int, originals):
+        self.last_rows = rows
+        out = []
+        names = self.aliases
+        for i in range(len(rows)):
+            if self.exprs is None:
+                value = originals(int(rows.src_index[i]) - base)
+            else:
+                value = {a: rows.aggs[j][i].item() for j, a in enumerate(names)}
+            out.append({"value": value, "timestamp": int(rows.win_start[i])})
+        return out
+
+    def process(self, records, watermark=-1):
+        keys, ts, cols, valid = self.columns(records)
+        base = self.op.stats()["records"]
+        wm = self.op.push(keys, ts, cols, valid, watermark=watermark)
+        return wm, self._forward(self.op.drain(), base, lambda k: records[k]["value"])
+
+    def process_json(self, buf: bytes, off, ts, watermark=-1, threads=0):
+        """One poll batch of raw JSON record values and their timestamps,
+        decoded by the native ingest without a key field; a SELECT * stream
+        forwards the records' own bytes."""
+        from . import ingest
+        if self._decoder is None:
+            self._decoder = ingest.Decoder(None, [(f, abi.HSG_F64 if fl else abi.HSG_I64, True) for f, fl in self.fields],
+                                           literal_forms=self.literal_forms)
+        keys, ts_out, cols, valid, _, _ = self._decoder.decode(None, buf, off, ts, threads)
+        base = self.op.stats()["records"]
+        wm = self.op.push(keys, ts_out, cols, valid, watermark=watermark)
+        return wm, self._forward(self.op.drain(), base, lambda k: bytes(buf[int(off[k]):int(off[k + 1])]))
+
+    def close(self):
+        if self._op is not None:
+            self._op.close()
+            self._op = None
+
+
 def select_view_result(rows, windowed: bool, session: bool, size_ms: int, names: Optional[Sequence[str]] = None):
     """The answer of SELECT ... FROM view WHERE key = x for one key's rows, as
     SelectViewPlan shapes it (hstream/src/HStream/Server/Handler.hs:287-323):
@@ -557,7 +705,8 @@ def joinTable(table: Table, joiner, records) -> list:
 def runTask(poll, table: Table, max_polls=None, sink=None):
     """Processor.hs:99-144 for one windowed aggregate: poll a batch, advance the
     task's stream time over every polled record, run the operator, forward
-    the changelog to `sink`. `poll()` returns a list of records or None."""
+    the changelog to `sink`. `poll()` returns a list of records or None.
+    `table` is a Table, or a Stream (the scalar SELECT chain)."""
     wm = -1  # tcTimestamp starts at -1 (Processor/Internal.hs:151)
     polls = 0
     while max_polls is None or polls < max_polls:

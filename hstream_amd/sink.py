@@ -70,7 +70,9 @@ def member_order(aliases: Sequence[str]) -> List[int]:
 
 class Sink:
     """members: [(alias, agg column or -1 for the GROUP BY value)], SELECT
-    order; the encoder writes them in aeson's order (member_order)."""
+    order; the encoder writes them in aeson's order (member_order). A select
+    op's sink has no key: keys = None, key_field = None, windowed = False, and
+    every key record it encodes is empty."""
 
     def __init__(self, op, keys, key_field: str, members: Sequence[Tuple[str, int]], windowed=True):
         self._L = _lib()
@@ -78,10 +80,11 @@ class Sink:
         n = len(members)
         self._aliases = (C.c_char_p * max(1, n))(*[a.encode() for a, _ in members])
         self._idx = (C.c_int32 * max(1, n))(*[j for _, j in members])
-        cfg = hsg_sink_config(windowed=1 if windowed else 0, n_members=n, key_field=key_field.encode(),
+        cfg = hsg_sink_config(windowed=1 if windowed else 0, n_members=n,
+                              key_field=key_field.encode() if key_field is not None else None,
                               aliases=self._aliases, agg_index=self._idx)
         h = C.c_void_p()
-        rc = self._L.hsg_sink_create(op._h, keys.handle, C.byref(cfg), C.byref(h))
+        rc = self._L.hsg_sink_create(op._h, keys.handle if keys is not None else None, C.byref(cfg), C.byref(h))
         if rc != abi.HSG_OK:
             raise abi.HStreamGpuError(rc, "hsg_sink_create")
         self._h = h

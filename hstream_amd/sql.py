@@ -20,6 +20,13 @@ the BNFC parser/validator are out of scope).
   compile_expr       a value expression of the SELECT list as the postfix value
                      program the op's map pass runs per record (include/
                      hstream_gpu.h hsg_map_expr): genRExprValue, Codegen.hs:290-301
+  gen_map_r          genMapR (Codegen.hs:349-353) for one record: the SELECT
+                     list's object {alias: Number}, strict as the reference's
+                     HashMap is; gen_select_rows is the whole RGroupByEmpty
+                     chain over a batch (the tests' reference)
+  gen_select_node    the RGroupByEmpty branch of genStreamBuilderWithStream
+                     (Codegen.hs:542-550): filter -> map -> having on one
+                     select op (hsg_op_create_select)
   compile_having     the HAVING condition as the same program over the
                      aggregates' aliases, run over the rows the op emits,
                      where the reference chains genFilteRNodeFromHaving
@@ -204,7 +211,8 @@ def unary_value(fn: int, x: Fraction) -> Fraction:
 
 
 def _is_number(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, float))
+    # (a Fraction: a Number of an object gen_map_r built, read again by HAVING)
+    return not isinstance(v, bool) and isinstance(v, (int, float, Fraction))
 
 
 def _field_name(e: RExprCol) -> str:
@@ -531,3 +539,78 @@ def gen_group_by_node(engine, sel: List[SelItem], group_by: RGroupBy, emit=abi.H
         return grouped.sessionWindowedBy(P.mkSessionWindows(diff_time_to_ms(w.seconds))).aggregate(aggs, mat, emit,
                                                                                                  where=where)
     raise ValueError("bad window")
+
+
+# ---- SELECT without GROUP BY (RGroupByEmpty, Codegen.hs:542-550) ----------------
+def _select_items(sel) -> List[Tuple[str, Any]]:
+    """The SELECT list as [(alias, value expression)]; ValueError for an
+    aggregate item (such a query has a GROUP BY branch of its own, or none)."""
+    out = []
+    for item in sel:
+        kind, *rest = item
+        if kind != "COL":
+            raise ValueError(f"aggregate {kind} in a SELECT without GROUP BY is not pushed down")
+        col = rest[0]
+        alias = rest[1] if len(rest) > 1 else None
+        if isinstance(col, str):
+            col = RExprCol(col, None, col)
+        out.append((alias or (_field_name(col) if isinstance(col, RExprCol) else col.name), col))
+    return out
+
+
+def gen_map_r(sel, value) -> dict:
+    """genMapR (Codegen.hs:349-353) for one record's value object: the object
+    {alias: Number} of the SELECT list's items (("COL", field or expression[,
+    alias])), each an exact Fraction. Strict, as Data.HashMap.Strict.fromList
+    is: raises (KeyError for a missing field, MathematicalError, TypeError)
+    where any expression does, and the caller drops the record. Aliases given
+    twice keep the later item, as fromList does."""
+    return {alias: _expr_value(e, value) for alias, e in _select_items(sel)}
+
+
+def gen_select_rows(sel, where, having, records) -> List[Tuple[int, int, Any]]:
+    """The RGroupByEmpty chain over one batch of records ({"value": object,
+    "timestamp": ts}): genFilterR where -> genMapR sel -> genFilterR having
+    over the mapped object, a record that throws anywhere being dropped as
+    runTask drops it. Returns [(index in the batch, timestamp, {alias:
+    Fraction})] in arrival order; sel = "*" forwards the record's own object."""
+    out = []
+    for i, rec in enumerate(records):
+        value = rec["value"]
+        try:
+            if not gen_filter_r(where, value):
+                continue
+            mapped = value if sel == "*" else gen_map_r(sel, value)
+            if not gen_filter_r(having, mapped):
+                continue
+        except (KeyError, TypeError, ArithmeticError):
+            continue
+        out.append((i, rec["timestamp"], mapped))
+    return out
+
+
+def gen_select_node(engine, sel, where=None, having=None, float_fields=(), functions: bool = False,
+                    literal_forms: bool = False, out_capacity: int = 0) -> P.Stream:
+    """The RGroupByEmpty dispatch: genFilterNode whr -> genMapNode sel ->
+    genFilteRNodeFromHaving hav (Codegen.hs:542-550) as one select op. The
+    batch's columns are the fields WHERE and the SELECT list read, in first-use
+    order. sel = "*" gives the index-only op (the host forwards the original
+    records). ValueError -- the query then stays on the host -- for an
+    aggregate item in the list, more than HSG_MAP_MAX_EXPRS items, duplicate
+    aliases, a HAVING that names no alias, and everything compile_where /
+    compile_expr / compile_having cannot say. The op is built on first use, so
+    the refusals need no GPU."""
+    items = None if sel == "*" else _select_items(sel)
+    fields: List[str] = where_fields(where) if where is not None else []
+    for _, e in items or []:
+        for f in where_fields(e):
+            if f not in fields:
+                fields.append(f)
+    st = P.Stream(engine, [(f, f in float_fields) for f in fields], literal_forms, out_capacity)
+    if where is not None:
+        st.filter(P.Where(where, float_fields, functions))
+    if items is not None:
+        st.map(items, functions)
+    if having is not None:
+        st.having(P.Having(having, functions))
+    return st

@@ -275,6 +275,68 @@ typedef struct {
   uint32_t aliased_cols;       /* expressions that are a caller's column (a single COL)         */
 } hsg_map_stats;
 
+/* Scalar SELECT: WHERE, the SELECT list and HAVING of a query without GROUP
+ * BY. The reference compiles SELECT a + b AS s, SQRT(c) AS r FROM src WHERE
+ * x > 3 EMIT CHANGES to a chain of stateless nodes (the RGroupByEmpty branch of
+ * genStreamBuilderWithStream, hstream-sql/src/HStream/SQL/Codegen.hs:542-550):
+ * genFilterNode whr, genMapNode sel, genFilteRNodeFromHaving hav, then the
+ * sink. A select op (hsg_op_create_select) is that chain for a whole poll
+ * batch: it keeps no state and has no group key. Per record, in arrival order:
+ *
+ *   1. A record whose key_id is HSG_KEY_NONE is skipped (it still moves stream
+ *      time). hsg_batch.key_id may be NULL for a select op: then every record
+ *      is live and its row carries HSG_KEY_NONE.
+ *   2. WHERE, the program above unchanged, over the raw columns; the record is
+ *      kept only on true. n_where == 0: every record is kept.
+ *   3. Expression j (a value program as in a map, 0 <= n_exprs <=
+ *      HSG_MAP_MAX_EXPRS, HSG_MAP_MAX_INS for all together) gives column j of
+ *      the row. Every expression is strict, whatever its flags say: the
+ *      reference builds the mapped object with Data.HashMap.Strict.fromList
+ *      (Codegen.hs:13, :349-353), so a missing field throws and runTask drops
+ *      the record. A record with any error expression emits no row.
+ *   4. HAVING, the same condition program with HSG_W_COL arg = expression arg,
+ *      typed by the expression's static type; an f64 value that is NaN is the
+ *      error value (the HAVING rule above). The row is kept only on true.
+ *      n_having == 0: every row is kept.
+ *   5. Kept rows are appended to the changelog, compacted, in arrival order:
+ *      key_id the record's, win_start = win_end = its ts (genMapR keeps the
+ *      record's timestamp), src_index the global index of the record (records
+ *      pushed since create / reset, as in every per-record changelog),
+ *      aggs[j] = expression j and hsg_rows.n_aggs = n_exprs. With
+ *      HSG_OPF_LITERAL_FORMS bit 2j of `form` is set iff expression j prints
+ *      as an integer: iff the derived bit 1 of "Computed columns" above is
+ *      clear (no operand had a literal with a negative exponent, or the rules
+ *      for constants and functions there); bit 2j + 1 is always 0. Without
+ *      the flag rows carry no form.
+ *
+ * n_exprs == 0 is SELECT * ... WHERE: the rows carry src_index only and the
+ * host forwards the original records by index.
+ *
+ * Stream time moves as for every op (inout_watermark, hsg_stats.records /
+ * batches). The room check comes ahead of the push and is the batch's worst
+ * case: pending + n > out_capacity gives HSG_E_CAPACITY and nothing is
+ * applied. The op has no state: hsg_state_rows gives 0, hsg_dump_state,
+ * hsg_view_get and hsg_table_join HSG_E_INVALID; every other call on an op
+ * works as on any op. On a sharded engine the op is local: no exchange, no
+ * collective, each rank filters its own slice. */
+typedef struct {
+  int32_t n_cols;           /* value columns carried by every batch (<= 8)                */
+  uint32_t flags;           /* HSG_OPF_LITERAL_FORMS or 0                                  */
+  const int32_t *col_types; /* n_cols hsg_col_type                                         */
+  uint64_t out_capacity;    /* changelog rows buffered between drains; 0 = the engine's
+                               batch_capacity                                             */
+} hsg_select_config;
+typedef struct {
+  uint64_t where_dropped;   /* live records of the last batch WHERE dropped                */
+  uint64_t where_dropped_total;
+  uint64_t expr_dropped;    /* ... WHERE kept and an expression's error value dropped      */
+  uint64_t expr_dropped_total;
+  uint64_t having_dropped;  /* ... both kept and HAVING dropped                            */
+  uint64_t having_dropped_total;
+  uint64_t emitted;         /* rows the last batch appended                                */
+  uint64_t emitted_total;
+} hsg_select_stats;
+
 typedef struct hsg_engine hsg_engine;
 typedef struct hsg_op hsg_op;
 
@@ -353,7 +415,8 @@ typedef struct {
   uint64_t n;
   int32_t mem;                  /* hsg_mem of every pointer below                        */
   int32_t n_cols;               /* must equal the op's n_cols                            */
-  const uint32_t *key_id;       /* dictionary-encoded group-by key, HSG_KEY_NONE = skip   */
+  const uint32_t *key_id;       /* dictionary-encoded group-by key, HSG_KEY_NONE = skip
+                                   (a select op's batch: may be NULL, every record live)  */
   const int64_t *ts;            /* event timestamp, ms (record header publish time)      */
   const void *const *cols;      /* n_cols arrays of int64_t or double                    */
   const uint8_t *const *valid;  /* n_cols presence arrays (1 byte/record, 0 = field absent);
@@ -513,6 +576,28 @@ int  hsg_prog_fn_class(const hsg_where_ins *prog, int32_t n);
 /* hsg_map_grid_threads of the map pass's kernel of function class fn_class
  * (0: hsg_map_grid_threads itself); 0 for a class that does not exist. */
 int  hsg_map_grid_threads_fn(int fn_class);
+/* Type-check the programs of a select op ("Scalar SELECT" above) against its
+ * value columns; pure host code (no GPU). where / having: hsg_where_check's
+ * rules (n == 0: none), the HAVING program's columns being the expressions,
+ * typed as hsg_map_check types them; exprs: hsg_map_check's rules, with
+ * n_exprs == 0 allowed. The messages begin "where: ", "map: " and "having: ";
+ * bad columns give "select: ...". */
+int  hsg_select_check(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
+                      const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols,
+                      char *err, size_t err_len);
+/* Create a select op. The programs are copied and fixed for the op's life;
+ * hsg_op_reset keeps them (and the cumulative counters) and drops the pending
+ * rows. HSG_E_INVALID with hsg_select_check's message in
+ * hsg_engine_last_error for programs it refuses, for a NULL cfg and for flags
+ * other than HSG_OPF_LITERAL_FORMS. Not collective. */
+int  hsg_op_create_select(hsg_engine *eng, const hsg_select_config *cfg, const hsg_where_ins *where, int32_t n_where,
+                          const hsg_map_expr *exprs, int32_t n_exprs, const hsg_where_ins *having, int32_t n_having,
+                          hsg_op **out);
+/* The select op's counters (hsg_stats keeps its size); HSG_E_INVALID for any other op. */
+int  hsg_op_select_stats(const hsg_op *op, hsg_select_stats *out);
+int  hsg_select_tile_rows(void);    /* records per tile of the kernel                        */
+int  hsg_select_grid_groups(void);  /* most workgroups one launch starts (function class 0):
+                                       a batch of more tiles has workgroups take a second   */
 void hsg_op_destroy(hsg_op *op);
 int  hsg_op_reset(hsg_op *op);            /* drop all state and pending rows          */
 const char *hsg_last_error(const hsg_op *op);

@@ -87,7 +87,11 @@ int  hsg_keydict_spelling_text(const hsg_keydict *d, uint32_t spell, char *buf, 
 
 /* ---- record decoder --------------------------------------------------------- */
 typedef struct {
-  const char *key_field;          /* GROUP BY column name (composeColName stream field) */
+  const char *key_field;          /* GROUP BY column name (composeColName stream field);
+                                     NULL: no key (the source of a select op, include/
+                                     hstream_gpu.h "Scalar SELECT"): every record that
+                                     decodes gets key id 0, a rejected one HSG_KEY_NONE,
+                                     and the dictionary (may be NULL) is not touched     */
   int32_t n_cols;                 /* aggregated fields, in hsg_batch column order       */
   const char *const *col_fields;
   const int32_t *col_types;       /* hsg_col_type                                       */

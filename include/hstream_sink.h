@@ -44,7 +44,10 @@ extern "C" {
 typedef struct {
   int32_t windowed;            /* 1: key = int64BE start ++ int64BE 0 ++ key object; 0: key object */
   int32_t n_members;           /* value object members (<= 16)                                   */
-  const char *key_field;       /* the key object is {key_field: value}                            */
+  const char *key_field;       /* the key object is {key_field: value}. NULL on a select op
+                                  (hsg_op_create_select), and only there: its source records
+                                  carry no key, every key record is empty (all key_off equal),
+                                  dict may be NULL, windowed is 0 and no agg_index is -1      */
   const char *const *aliases;  /* member names, SELECT order                                      */
   const int32_t *agg_index;    /* changelog aggregate column of each member; -1 = the GROUP BY
                                   value itself (SELECT of the grouping column)                    */

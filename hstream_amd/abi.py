@@ -525,9 +525,36 @@ class hsg_join_rows(C.Structure):
     ]
 
 
+HSG_JOIN_MAX_COLS = 8
+
+
+class hsg_join_values(C.Structure):
+    _fields_ = [("n_cols", C.c_int32 * 2), ("col_types", (C.c_int32 * 8) * 2)]
+
+
+class hsg_join_cols(C.Structure):
+    _fields_ = [("cols", C.POINTER(C.c_void_p)), ("valid", C.POINTER(C.c_void_p))]
+
+
+class hsg_join_joined(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_uint64),
+        ("mem", C.c_int32),
+        ("key_col", C.c_int32),
+        ("key_id", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("cols", C.POINTER(C.c_void_p)),
+        ("valid", C.POINTER(C.c_void_p)),
+        ("this_handle", C.c_void_p),
+        ("other_handle", C.c_void_p),
+        ("join_key", C.c_void_p),
+    ]
+
+
 # Every symbol include/hstream_join.h declares.
 JOIN_SYMBOLS = ["hsg_join_create", "hsg_join_destroy", "hsg_join_last_error", "hsg_join_push", "hsg_join_pending",
-                "hsg_join_drain", "hsg_join_state_rows"]
+                "hsg_join_drain", "hsg_join_state_rows", "hsg_join_create_valued", "hsg_join_push_valued",
+                "hsg_join_drain_batch", "hsg_join_value_rows", "hsg_join_value_stride"]
 
 
 # void (*hsg_done_fn)(void *ctx, int rc)

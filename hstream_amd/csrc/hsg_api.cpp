@@ -1415,6 +1415,7 @@ bool op_is_select(const hsg_op *op) { return op && op->select; }
 namespace hsg {
 // For the join (join.cpp): the engine's device.
 int engine_device(const hsg_engine *e) { return e ? e->device : 0; }
+int engine_nranks(const hsg_engine *e) { return e ? e->nranks : 1; }
 int engine_split_comm(hsg_engine *e, Comm **out, int *rank, int *nranks, std::string &err) {
   *out = nullptr;
   *rank = e ? e->rank : 0;

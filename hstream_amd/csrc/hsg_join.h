@@ -86,4 +86,49 @@ void launch_join_tkeep(hipStream_t s, const TEnt *T, uint64_t n, uint32_t *flag)
 void launch_join_tkeep_write(hipStream_t s, const TEnt *T, uint64_t n, const uint32_t *flag, const uint64_t *off,
                              TEnt *out);
 
+// ---- valued join (k_join_vals.hip) -----------------------------------------
+// One arena of array-of-struct value rows shared by both sides, row = the
+// record's arrival number over the join's life (its handle). A row is `stride`
+// 8-byte words, stride in {2, 4, 8, 16}: words 0 .. c-1 are the side's values,
+// word c holds the valid bytes (byte k: column k), the rest is zero. The
+// arena is 256-byte aligned and the stride a power of two <= 128 bytes, so a
+// row never straddles a 128-byte line (as TwTable's slots).
+constexpr int kJoinMaxCols = 8;
+
+__host__ __device__ inline uint32_t jv_stride(int c0, int c1) {
+  const int need = (c0 > c1 ? c0 : c1) + 1;
+  uint32_t s = 2;
+  while ((int)s < need) s *= 2;
+  return s;
+}
+
+struct JvAppend {
+  uint64_t n, used;          // records of the batch; rows in use before it
+  const uint8_t *side;
+  const void *cols[kJoinMaxCols];
+  const uint8_t *valid[kJoinMaxCols];  // nullptr: all present
+  int nc[2];
+  uint64_t *arena;
+  uint64_t *handle;          // [n] <- used + i (launch_join_build reads it)
+};
+void launch_jv_append(hipStream_t s, const JvAppend &a, uint32_t stride);
+
+struct JvGather {
+  uint64_t n, used;          // pending rows; value rows in use
+  const uint64_t *this_h, *other_h;
+  const uint32_t *jkey;
+  const int64_t *ts;
+  const uint64_t *arena;
+  int nc[2];
+  int key_col;               // -1: the join key
+  // outputs, lane = row; a nullptr is skipped
+  uint64_t *col_a[kJoinMaxCols], *col_b[kJoinMaxCols];  // this side's / the other side's columns
+  uint8_t *val_a[kJoinMaxCols], *val_b[kJoinMaxCols];
+  uint32_t *key_id;
+  int64_t *o_ts;
+  uint64_t *o_this, *o_other;
+  uint32_t *o_jkey;
+};
+void launch_jv_gather(hipStream_t s, const JvGather &g, uint32_t stride);
+
 }  // namespace hsg

@@ -20,6 +20,7 @@ using namespace hsg;
 namespace hsg {
 // hsg_api.cpp
 int engine_device(const hsg_engine *e);
+int engine_nranks(const hsg_engine *e);
 // a communicator of the engine's ranks for one sharded object (nullptr, rank
 // 0 of 1 on a single-rank engine)
 int engine_split_comm(hsg_engine *e, Comm **out, int *rank, int *nranks, std::string &err);
@@ -71,6 +72,18 @@ struct hsg_join {
   uint32_t *g_key = nullptr, *g_jkey = nullptr;
   int64_t *g_ts = nullptr;
   uint64_t *g_handle = nullptr;
+  // valued (hsg_join_create_valued): the records' value rows (hsg_join.h),
+  // row = the record's arrival number over the join's life = its handle
+  bool valued = false;
+  int nc[2] = {0, 0};
+  int ctype[2][kJoinMaxCols] = {};
+  uint32_t stride = 0;            // 8-byte words per row
+  uint64_t *arena = nullptr;
+  uint64_t val_used = 0, val_cap = 0;
+  uint64_t *st_cols = nullptr;    // [max(nc) * batch_cap] a host batch's columns
+  uint8_t *st_valid = nullptr;    // [max(nc) * batch_cap]
+  uint8_t *stage = nullptr;       // joined columns of a host drain
+  uint64_t stage_cap = 0;         // (rows)
 };
 
 namespace {
@@ -105,6 +118,10 @@ void free_join(hsg_join *j) {
   void *xptrs[] = {j->d_n, j->d_nall, j->d_off, j->r_side, j->r_key, j->r_jkey, j->r_ts, j->r_handle,
                    j->g_side, j->g_key, j->g_jkey, j->g_ts, j->g_handle};
   for (void *p : xptrs) dfree(p);
+  dfree(j->arena);
+  dfree(j->st_cols);
+  dfree(j->st_valid);
+  dfree(j->stage);
   if (j->h_nall) hipHostFree(j->h_nall);
   if (j->comm) comm_destroy(j->comm);
   if (j->h_tot) hipHostFree(j->h_tot);
@@ -180,6 +197,43 @@ int ensure_out(hsg_join *j, uint64_t need) {
   dfree(j->out.ts);
   j->out = o;
   j->out_cap = c;
+  return HSG_OK;
+}
+
+// value arena with room for `need` rows (rows in use kept): doubles with a
+// device-to-device copy on the join's stream
+int ensure_vals(hsg_join *j, uint64_t need) {
+  if (need <= j->val_cap) return HSG_OK;
+  uint64_t c = j->val_cap ? j->val_cap : j->batch_cap;
+  while (c < need) c *= 2;
+  uint64_t *a = nullptr;
+  JTRY(dmalloc(a, c * j->stride));
+  hipError_t e = hipSuccess;
+  if (j->val_used)
+    e = hipMemcpyAsync(a, j->arena, j->val_used * j->stride * 8, hipMemcpyDeviceToDevice, j->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(j->stream);
+  if (e != hipSuccess) {
+    dfree(a);
+    JTRY(e);
+  }
+  dfree(j->arena);
+  j->arena = a;
+  j->val_cap = c;
+  return HSG_OK;
+}
+
+// staging of a host drain: per row 8 bytes per joined column, the key id, one
+// valid byte per column
+uint64_t stage_row_bytes(const hsg_join *j) { return 9ull * (uint64_t)(j->nc[0] + j->nc[1]) + 4; }
+int ensure_stage(hsg_join *j, uint64_t rows) {
+  if (rows <= j->stage_cap) return HSG_OK;
+  uint64_t c = j->stage_cap ? j->stage_cap : (1u << 16);
+  while (c < rows) c *= 2;
+  dfree(j->stage);
+  j->stage = nullptr;
+  j->stage_cap = 0;
+  JTRY(dmalloc(j->stage, c * stage_row_bytes(j)));
+  j->stage_cap = c;
   return HSG_OK;
 }
 
@@ -279,15 +333,23 @@ extern "C" void hsg_join_destroy(hsg_join *j) { free_join(j); }
 
 extern "C" const char *hsg_join_last_error(const hsg_join *j) { return j ? j->err.c_str() : "null join"; }
 
-extern "C" int hsg_join_push(hsg_join *j, const hsg_join_batch *b) {
-  if (!j || !b) return HSG_E_INVALID;
+namespace {
+
+// hsg_join_push (cols == nullptr) / hsg_join_push_valued
+int push_impl(hsg_join *j, const hsg_join_batch *b, const hsg_join_cols *cols) {
   if (b->n > j->batch_cap) {
     j->err = "batch larger than batch_capacity";
     return HSG_E_CAPACITY;
   }
   if (b->mem != HSG_MEM_HOST && b->mem != HSG_MEM_DEVICE) return HSG_E_INVALID;
   uint64_t n = b->n;
-  if (n && (!b->side || !b->key_id || !b->join_key || !b->ts || !b->handle)) return HSG_E_INVALID;
+  if (n && (!b->side || !b->key_id || !b->join_key || !b->ts || (!cols && !b->handle))) return HSG_E_INVALID;
+  const int vc = j->nc[0] > j->nc[1] ? j->nc[0] : j->nc[1];  // (valued: the columns a batch carries)
+  if (cols && n && vc) {
+    if (!cols->cols) return HSG_E_INVALID;
+    for (int c = 0; c < vc; ++c)
+      if (!cols->cols[c]) return HSG_E_INVALID;
+  }
   if (!n && j->nranks == 1) return HSG_OK;  // (sharded: every rank joins the all-gather, empty slice or not)
   try {
     JTRY(hipSetDevice(j->device));
@@ -304,7 +366,7 @@ extern "C" int hsg_join_push(hsg_join *j, const hsg_join_batch *b) {
       JTRY(hipMemcpyAsync(j->st_key, b->key_id, n * 4, k, s));
       JTRY(hipMemcpyAsync(j->st_jkey, b->join_key, n * 4, k, s));
       JTRY(hipMemcpyAsync(j->st_ts, b->ts, n * 8, k, s));
-      JTRY(hipMemcpyAsync(j->st_handle, b->handle, n * 8, k, s));
+      if (!cols) JTRY(hipMemcpyAsync(j->st_handle, b->handle, n * 8, k, s));
       db.side = j->st_side, db.key = j->st_key, db.jkey = j->st_jkey, db.ts = j->st_ts, db.handle = j->st_handle;
     }
     if (j->nranks > 1) {
@@ -349,8 +411,30 @@ extern "C" int hsg_join_push(hsg_join *j, const hsg_join_batch *b) {
       db.n = n;
       db.side = j->g_side, db.key = j->g_key, db.jkey = j->g_jkey, db.ts = j->g_ts, db.handle = j->g_handle;
     }
-    int rc = ensure_state(j, j->nR + n, j->nT + n);
+    int rc = cols ? ensure_vals(j, j->val_used + n) : HSG_OK;
     if (rc != HSG_OK) return rc;
+    rc = ensure_state(j, j->nR + n, j->nT + n);
+    if (rc != HSG_OK) return rc;
+    if (cols) {
+      // the value rows at val_used + i and the handles the build reads
+      JvAppend a = {};
+      a.n = n, a.used = j->val_used, a.side = db.side, a.nc[0] = j->nc[0], a.nc[1] = j->nc[1];
+      a.arena = j->arena, a.handle = j->st_handle;
+      for (int c = 0; c < vc; ++c) {
+        const uint8_t *v = cols->valid ? cols->valid[c] : nullptr;
+        if (b->mem == HSG_MEM_DEVICE) {
+          a.cols[c] = cols->cols[c], a.valid[c] = v;
+        } else {
+          uint64_t *dc = j->st_cols + (uint64_t)c * j->batch_cap;
+          uint8_t *dv = j->st_valid + (uint64_t)c * j->batch_cap;
+          JTRY(hipMemcpyAsync(dc, cols->cols[c], n * 8, hipMemcpyHostToDevice, s));
+          if (v) JTRY(hipMemcpyAsync(dv, v, n, hipMemcpyHostToDevice, s));
+          a.cols[c] = dc, a.valid[c] = v ? dv : nullptr;
+        }
+      }
+      launch_jv_append(s, a, j->stride);
+      db.handle = j->st_handle;
+    }
     launch_join_build(s, db, j->braw);
     // 1. the batch by (record key, side, ts, arrival), merged into the state
     static const int m_passes[4] = {0, 1, 2, 3};
@@ -398,10 +482,151 @@ extern "C" int hsg_join_push(hsg_join *j, const hsg_join_batch *b) {
     j->nR = j->h_tot[2];
     j->nT = j->h_tot[3];
     j->pending += rows;
+    if (cols) j->val_used += n;
     return HSG_OK;
   } catch (const std::bad_alloc &) {
     return HSG_E_OOM;
   }
+}
+
+}  // namespace
+
+extern "C" int hsg_join_push(hsg_join *j, const hsg_join_batch *b) {
+  if (!j || !b) return HSG_E_INVALID;
+  if (j->valued) {
+    j->err = "hsg_join_push on a valued join (hsg_join_push_valued)";
+    return HSG_E_INVALID;
+  }
+  return push_impl(j, b, nullptr);
+}
+
+extern "C" int hsg_join_push_valued(hsg_join *j, const hsg_join_batch *b, const hsg_join_cols *cols) {
+  if (!j || !b || !cols) return HSG_E_INVALID;
+  if (!j->valued) {
+    j->err = "hsg_join_push_valued on a plain join (hsg_join_create_valued)";
+    return HSG_E_INVALID;
+  }
+  return push_impl(j, b, cols);
+}
+
+extern "C" uint64_t hsg_join_value_stride(int32_t c0, int32_t c1) {
+  if (c0 < 0 || c1 < 0 || c0 > kJoinMaxCols || c1 > kJoinMaxCols || c0 + c1 > kJoinMaxCols) return 0;
+  return jv_stride(c0, c1);
+}
+
+extern "C" int hsg_join_create_valued(hsg_engine *eng, const hsg_join_config *cfg, const hsg_join_values *vals,
+                                      hsg_join **out) {
+  if (!eng || !cfg || !vals || !out) return HSG_E_INVALID;
+  *out = nullptr;
+  if (!hsg_join_value_stride(vals->n_cols[0], vals->n_cols[1])) return HSG_E_INVALID;
+  for (int sd = 0; sd < 2; ++sd)
+    for (int c = 0; c < vals->n_cols[sd]; ++c)
+      if (vals->col_types[sd][c] != HSG_I64 && vals->col_types[sd][c] != HSG_F64) return HSG_E_INVALID;
+  // a sharded valued join is out of scope: refused before any collective, alike on every rank
+  if (engine_nranks(eng) > 1) return HSG_E_INVALID;
+  hsg_join *j = nullptr;
+  int rc = hsg_join_create(eng, cfg, &j);
+  if (rc != HSG_OK) return rc;
+  j->valued = true;
+  for (int sd = 0; sd < 2; ++sd) {
+    j->nc[sd] = vals->n_cols[sd];
+    for (int c = 0; c < j->nc[sd]; ++c) j->ctype[sd][c] = vals->col_types[sd][c];
+  }
+  j->stride = jv_stride(j->nc[0], j->nc[1]);
+  const uint64_t vc = (uint64_t)(j->nc[0] > j->nc[1] ? j->nc[0] : j->nc[1]);
+  hipError_t e = hipSetDevice(j->device);
+  if (e == hipSuccess) e = dmalloc(j->st_cols, vc * j->batch_cap);
+  if (e == hipSuccess) e = dmalloc(j->st_valid, vc * j->batch_cap);
+  if (e != hipSuccess) {
+    free_join(j);
+    return e == hipErrorOutOfMemory ? HSG_E_OOM : HSG_E_DEVICE;
+  }
+  rc = ensure_vals(j, j->batch_cap);
+  if (rc != HSG_OK) {
+    free_join(j);
+    return rc;
+  }
+  *out = j;
+  return HSG_OK;
+}
+
+extern "C" int hsg_join_value_rows(const hsg_join *j, uint64_t *used, uint64_t *capacity) {
+  if (!j || !used || !capacity || !j->valued) return HSG_E_INVALID;
+  *used = j->val_used;
+  *capacity = j->val_cap;
+  return HSG_OK;
+}
+
+extern "C" int hsg_join_drain_batch(hsg_join *j, hsg_join_joined *o, uint64_t *n_out) {
+  if (!j || !o || !n_out) return HSG_E_INVALID;
+  if (!j->valued) {
+    j->err = "hsg_join_drain_batch on a plain join (hsg_join_create_valued)";
+    return HSG_E_INVALID;
+  }
+  *n_out = j->pending;
+  if (o->capacity < j->pending) return HSG_E_CAPACITY;
+  if (o->mem != HSG_MEM_HOST && o->mem != HSG_MEM_DEVICE) return HSG_E_INVALID;
+  const int c0 = j->nc[0], c1 = j->nc[1], C = c0 + c1;
+  if (o->key_col < -1 || o->key_col >= C) {
+    j->err = "key_col names no joined column";
+    return HSG_E_INVALID;
+  }
+  if (o->key_col >= 0 &&
+      (o->key_col < c0 ? j->ctype[0][o->key_col] : j->ctype[1][o->key_col - c0]) != HSG_I64) {
+    j->err = "key_col names an f64 column";
+    return HSG_E_INVALID;
+  }
+  const uint64_t n = j->pending;
+  if (n && C && !o->cols) return HSG_E_INVALID;
+  if (n) {
+    JTRY(hipSetDevice(j->device));
+    hipStream_t s = j->stream;
+    const bool host = o->mem == HSG_MEM_HOST;
+    JvGather g = {};
+    g.n = n, g.used = j->val_used;
+    g.this_h = j->out.this_h, g.other_h = j->out.other_h, g.jkey = j->out.jkey, g.ts = j->out.ts;
+    g.arena = j->arena, g.nc[0] = c0, g.nc[1] = c1, g.key_col = o->key_col;
+    // (host: the arrays are gathered into staging of the same shape, column k at k * 8n)
+    uint64_t *s_cols = nullptr;
+    uint32_t *s_key = nullptr;
+    uint8_t *s_valid = nullptr;
+    if (host) {
+      const int rc = ensure_stage(j, n);
+      if (rc != HSG_OK) return rc;
+      s_cols = (uint64_t *)j->stage;
+      s_key = (uint32_t *)(j->stage + 8ull * C * n);
+      s_valid = j->stage + 8ull * C * n + 4ull * n;
+    }
+    for (int k = 0; k < C; ++k) {
+      uint64_t *col = (uint64_t *)o->cols[k];
+      uint8_t *val = o->valid ? o->valid[k] : nullptr;
+      if (host) {
+        col = col ? s_cols + (uint64_t)k * n : nullptr;
+        val = val ? s_valid + (uint64_t)k * n : nullptr;
+      }
+      if (k < c0) g.col_a[k] = col, g.val_a[k] = val;
+      else g.col_b[k - c0] = col, g.val_b[k - c0] = val;
+    }
+    g.key_id = o->key_id ? (host ? s_key : o->key_id) : nullptr;
+    if (!host) g.o_ts = o->ts, g.o_this = o->this_handle, g.o_other = o->other_handle, g.o_jkey = o->join_key;
+    launch_jv_gather(s, g, j->stride);
+    if (host) {
+      const hipMemcpyKind k = hipMemcpyDeviceToHost;
+      for (int c = 0; c < C; ++c) {
+        if (o->cols[c]) JTRY(hipMemcpyAsync(o->cols[c], s_cols + (uint64_t)c * n, n * 8, k, s));
+        if (o->valid && o->valid[c]) JTRY(hipMemcpyAsync(o->valid[c], s_valid + (uint64_t)c * n, n, k, s));
+      }
+      if (o->key_id) JTRY(hipMemcpyAsync(o->key_id, s_key, n * 4, k, s));
+      if (o->ts) JTRY(hipMemcpyAsync(o->ts, j->out.ts, n * 8, k, s));
+      if (o->this_handle) JTRY(hipMemcpyAsync(o->this_handle, j->out.this_h, n * 8, k, s));
+      if (o->other_handle) JTRY(hipMemcpyAsync(o->other_handle, j->out.other_h, n * 8, k, s));
+      if (o->join_key) JTRY(hipMemcpyAsync(o->join_key, j->out.jkey, n * 4, k, s));
+    }
+    JTRY(hipStreamSynchronize(s));
+    JTRY(hipGetLastError());
+  }
+  j->pending = 0;
+  return HSG_OK;
 }
 
 extern "C" int hsg_join_pending(const hsg_join *j, uint64_t *n) {

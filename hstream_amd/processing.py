@@ -14,6 +14,7 @@ Names and argument meaning follow hstream-processing (Yu-zh/hstream):
   runTask (poll loop + stream time)                  Processor.hs:99-144
   Stream.filter / Stream.map                         Stream.hs:151-194 (the scalar SELECT
                                                      chain, Codegen.hs:542-550)
+  joinStream (the SQL JOIN plan's, with genJoiner)   Stream.hs:222-300, Codegen.hs:253-266
   time-window / session key serdes                   TimeWindows.hs:68-93,
                                                      hstream-sql/.../Codegen/Boilerplate.hs:60-88
 
@@ -719,3 +720,182 @@ def runTask(poll, table: Table, max_polls=None, sink=None):
                 sink(r)
         polls += 1
     return wm
+
+
+# ---------------------------------------------------------------------------
+# stream-stream join (Stream.joinStream)
+# ---------------------------------------------------------------------------
+def join_stream_rows(before_ms: int, after_ms: int, records, f1: str, f2: str):
+    """joinStreamProcessor (Stream.hs:267-300) over both streams' records in
+    arrival order, one at a time on the host: what joinStream forwards, as
+    (index of this side's record, index of the other side's, timestamp) in
+    forwarding order. Each record is {"side": 0 | 1, "key": record key or None,
+    "value": object, "timestamp": ts}; the join key is value[f1] (side 0) or
+    value[f2] (side 1). A record without a key is dropped before it is stored
+    (fromJust, :283); the range over the other store includes its end points
+    only when that store holds both end timestamps (tksRange, Store.hs:355-372);
+    a missing join field on either side ends the record's scan at that
+    candidate (the key selector throws, Codegen.hs:242-244). Pure: no GPU."""
+    import bisect
+    stores = [dict(), dict()]   # side -> ts -> {canonical key: record index}
+    tls = [[], []]              # side -> sorted timestamps held
+    fields = (f1, f2)
+    out = []
+    for i, r in enumerate(records):
+        if r.get("key") is None:
+            continue
+        side, ts, key = int(r["side"]), int(r["timestamp"]), _canon(r["key"])
+        st = stores[side]
+        if ts not in st:
+            st[ts] = {}
+            bisect.insort(tls[side], ts)
+        st[ts][key] = i
+        b, a = (before_ms, after_ms) if side == 0 else (after_ms, before_ms)
+        lo, hi = ts - b, ts + a
+        ost, tl = stores[1 - side], tls[1 - side]
+        if lo in ost and hi > lo and hi in ost:
+            i0, i1 = bisect.bisect_left(tl, lo), bisect.bisect_right(tl, hi)
+        else:
+            i0, i1 = bisect.bisect_right(tl, lo), bisect.bisect_left(tl, hi)
+        for t in tl[i0:i1]:
+            k = ost[t].get(key)
+            if k is None:
+                continue
+            mine, theirs = r["value"], records[k]["value"]
+            if fields[side] not in mine or fields[1 - side] not in theirs:
+                break
+            if _canon(mine[fields[side]]) == _canon(theirs[fields[1 - side]]):
+                out.append((i, k, max(ts, t)) if side == 0 else (k, i, max(ts, t)))
+    return out
+
+
+class JoinedStream:
+    """Stream.joinStream (Stream.hs:222-250) with the SQL plan's joiner
+    (genJoiner: the union of both values under "s1.f" / "s2.g"), backed by one
+    valued GPU join: the join keeps the named numeric fields of every record in
+    HBM and drains the joined records as columns.
+
+    process(records) runs one poll batch of both streams' records ({"stream":
+    s1 | s2 (or "side": 0 | 1), "key": record key or None, "value": object,
+    "timestamp": ts}) and returns the joined records as the reference forwards
+    them: {"key": {"SelectedKey": join key}, "value": {"s1.f": ..., "s2.g":
+    ...}, "timestamp": max of the two}. The value holds the named fields only.
+    process_into(records, op) leaves the joined batch on the device and pushes
+    it into a Table's / Stream's op whose fields are `names`."""
+
+    def __init__(self, engine, s1, s2, f1, f2, fields1, fields2, before_ms, after_ms, batch_capacity=1 << 20,
+                 keys=None, join_keys=None):
+        from .join import Join
+        norm = lambda fs: [(f, False) if isinstance(f, str) else (f[0], bool(f[1])) for f in fs]
+        self.s = (s1, s2)
+        self.f = (f1, f2)
+        self.fields = (norm(fields1), norm(fields2))
+        self.names = [f"{s1}.{f}" for f, _ in self.fields[0]] + [f"{s2}.{f}" for f, _ in self.fields[1]]
+        self.float_names = [n for n, (_, fl) in zip(self.names, self.fields[0] + self.fields[1]) if fl]
+        self.keys = keys if keys is not None else KeyDict()                  # record keys
+        self.join_keys = join_keys if join_keys is not None else KeyDict()   # join keys: a drained batch's key_id
+        self.join = Join(engine, before_ms, after_ms, batch_capacity,
+                         cols=tuple([abi.HSG_F64 if fl else abi.HSG_I64 for _, fl in fs] for fs in self.fields))
+
+    def _side(self, rec):
+        if "side" in rec:
+            return int(rec["side"])
+        if self.s[0] == self.s[1]:
+            raise ValueError("a self-join's records name their side: {'side': 0 | 1}")
+        return 0 if rec["stream"] == self.s[0] else 1
+
+    def columns(self, records):
+        """The poll batch as the arrays of Join.push: side, record key id, join
+        key id, ts, value columns (the wider side's count; int64 storage, an f64
+        field's bits) and their valid bytes. A present value that is no Number
+        raises ValueError: the join carries numeric columns only."""
+        n = len(records)
+        vc = max(len(self.fields[0]), len(self.fields[1]))
+        side = np.zeros(n, np.uint8)
+        key = np.full(n, abi.HSG_KEY_NONE, np.uint32)
+        jkey = np.full(n, abi.HSG_KEY_NONE, np.uint32)
+        ts = np.empty(n, np.int64)
+        cols = [np.zeros(n, np.int64) for _ in range(vc)]
+        valid = [np.zeros(n, np.uint8) for _ in range(vc)]
+        for i, rec in enumerate(records):
+            sd = side[i] = self._side(rec)
+            value = rec["value"]
+            ts[i] = rec["timestamp"]
+            if rec.get("key") is not None:
+                key[i] = self.keys.encode(rec["key"])
+            if self.f[sd] in value:
+                jkey[i] = self.join_keys.encode(value[self.f[sd]])
+            for c, (f, fl) in enumerate(self.fields[sd]):
+                if f not in value:
+                    continue
+                v = value[f]
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"field {f}: the GPU join carries numeric columns only")
+                if fl:
+                    cols[c][i:i + 1].view(np.float64)[0] = float(v)
+                else:
+                    cols[c][i] = int(v)
+                valid[c][i] = 1
+        return side, key, jkey, ts, cols, valid
+
+    def push(self, records):
+        side, key, jkey, ts, cols, valid = self.columns(records)
+        self.join.push(side, key, jkey, ts, cols=cols, valid=valid)
+
+    def process(self, records):
+        self.push(records)
+        b = self.join.drain_batch(optional=("valid",))
+        s1, s2 = self.s
+        names = [(f"{s1}.{f}", 0) for f, _ in self.fields[0]] + [(f"{s2}.{f}", 1) for f, _ in self.fields[1]]
+        out = []
+        for i in range(len(b.ts)):
+            value = {}
+            for c in reversed(range(len(names))):  # (left-biased union: this side's value is written last)
+                if b.valid[c][i] & 1:
+                    value[names[c][0]] = b.cols[c][i].item()
+            out.append({"key": {"SelectedKey": self.join_keys.decode(int(b.key_id[i]))},
+                        "value": {nm: value[nm] for nm, _ in names if nm in value}, "timestamp": int(b.ts[i])})
+        return out
+
+    def process_into(self, records, target, key_col=None, watermark=-1):
+        """One poll batch through the join and its joined rows, still on the
+        device, into `target`: a Table (gen_group_by_node) or a Stream
+        (gen_select_node) whose fields are among `names`; its op reads the
+        drained tensors in place (HSG_MEM_DEVICE), each of its columns the
+        joined column of that name. The group key of a Table: its key field
+        names a joined i64 column, whose value is the key id (a key outside
+        0 .. 2^32 - 2 or absent is HSG_KEY_NONE: the reference drops such a
+        record too, getFieldByName throws); key_col = -1 groups by the join
+        key instead, as ids of join_keys. Returns the stream time; the rows
+        wait in target.op (drain)."""
+        fields = target.fields
+        index = []
+        for f, fl in fields:
+            if f not in self.names:
+                raise ValueError(f"{f} is not a column of the joined stream {self.names}")
+            index.append(self.names.index(f))
+            if fl != (f in self.float_names):
+                raise ValueError(f"{f}: the joined column and the target's field differ in type")
+        if key_col is None:
+            key_col = -1
+            if isinstance(target, Table):
+                kf = target.grouped.key_field
+                if kf not in self.names or kf in self.float_names:
+                    raise ValueError(f"GROUP BY {kf}: not an i64 column of the joined stream")
+                key_col = self.names.index(kf)
+        self.push(records)
+        b = self.join.drain_batch(key_col=key_col, device=True, optional=("valid",))
+        return target.op.push(b.key_id, b.ts, [b.cols[k] for k in index], [b.valid[k] for k in index],
+                              watermark=watermark)
+
+    def close(self):
+        self.join.close()
+
+
+def joinStream(engine, s1, s2, f1, f2, fields1, fields2, before_ms, after_ms, batch_capacity=1 << 20,
+               keys=None, join_keys=None) -> JoinedStream:
+    """Stream.joinStream (Stream.hs:222-250) as the SQL plan calls it
+    (Codegen.hs:259-266): stream s1 joined with s2 on s1.f1 = s2.f2 within
+    [ts - before_ms, ts + after_ms], the joiner being genJoiner over the named
+    numeric fields of each side. See JoinedStream."""
+    return JoinedStream(engine, s1, s2, f1, f2, fields1, fields2, before_ms, after_ms, batch_capacity, keys, join_keys)

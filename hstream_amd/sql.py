@@ -31,6 +31,11 @@ the BNFC parser/validator are out of scope).
                      aggregates' aliases, run over the rows the op emits,
                      where the reference chains genFilteRNodeFromHaving
                      behind an unwindowed aggregate (Codegen.hs:524-529)
+  gen_joiner         genJoiner, Internal/Codegen.hs:62-67
+  RFromJoin /        the RFromJoin branch of genStreamWithSourceStream
+  gen_join_node      (Codegen.hs:253-266) as one valued GPU join whose drained
+                     batches feed gen_select_node / gen_group_by_node on the
+                     device; gen_join_rows is its host mirror (the tests' reference)
 """
 import math
 from dataclasses import dataclass
@@ -614,3 +619,74 @@ def gen_select_node(engine, sel, where=None, having=None, float_fields=(), funct
     if having is not None:
         st.having(P.Having(having, functions))
     return st
+
+
+# ---- FROM s1 INNER JOIN s2 WITHIN (...) ON s1.a = s2.b (Codegen.hs:219-266) ------
+@dataclass(frozen=True)
+class RFromJoin:
+    """RFromJoin (s1, f1) (s2, f2) RJoinInner win (AST.hs:266): the two streams,
+    the join field of each, and the WITHIN interval in seconds (a DiffTime)."""
+    s1: str
+    f1: str
+    s2: str
+    f2: str
+    seconds: int
+    join_type: str = "RJoinInner"
+
+
+def gen_joiner(s1: str, s2: str, o1: dict, o2: dict) -> dict:
+    """genJoiner (Internal/Codegen.hs:62-67): the union of both values with the
+    field names prefixed "s1." / "s2.". HM.union is left-biased, so where a
+    self-join (s1 == s2) gives both sides equal names, this side's value wins."""
+    out = {f"{s2}.{k}": v for k, v in o2.items()}
+    out.update({f"{s1}.{k}": v for k, v in o1.items()})
+    return out
+
+
+def gen_join_windows(frm: RFromJoin) -> Tuple[int, int]:
+    """genJoinWindows (Codegen.hs:232-240): (jwBeforeMs, jwAfterMs), both the interval."""
+    w = diff_time_to_ms(frm.seconds)
+    return w, w
+
+
+def _check_join(frm: RFromJoin):
+    if frm.join_type != "RJoinInner":
+        raise ValueError(f"join type {frm.join_type}: Impossible happened")  # Codegen.hs:267-268
+
+
+def gen_join_rows(frm: RFromJoin, records, windows: Optional[Tuple[int, int]] = None) -> List[dict]:
+    """The host mirror of the JOIN plan's source (genStreamWithSourceStream,
+    Codegen.hs:253-266) over `records` of both streams in arrival order, each
+    {"stream": s1 | s2, "key": record key or None, "value": object,
+    "timestamp": ts}: joinStream's rows (processing.join_stream_rows) with
+    genJoiner applied. Returns, in the order the reference forwards them,
+    {"key": {"SelectedKey": join key}, "value": joined object, "timestamp":
+    max of the two} -- the records gen_select_rows / a GROUP BY then read.
+    windows = (before_ms, after_ms) replaces genJoinWindows' (the DSL's
+    joinStream takes any JoinWindows)."""
+    _check_join(frm)
+    before, after = windows if windows is not None else gen_join_windows(frm)
+    if frm.s1 == frm.s2 and any("side" not in r for r in records):
+        raise ValueError("a self-join's records name their side: {'side': 0 | 1}")
+    recs = [r if "side" in r else dict(r, side=0 if r["stream"] == frm.s1 else 1) for r in records]
+    out = []
+    for i, k, ts in P.join_stream_rows(before, after, recs, frm.f1, frm.f2):
+        a, b = records[i], records[k]
+        out.append({"key": {"SelectedKey": a["value"][frm.f1]}, "value": gen_joiner(frm.s1, frm.s2, a["value"], b["value"]),
+                    "timestamp": ts})
+    return out
+
+
+def gen_join_node(engine, frm: RFromJoin, fields1: Sequence, fields2: Sequence, batch_capacity: int = 1 << 20,
+                  windows: Optional[Tuple[int, int]] = None):
+    """The RFromJoin branch of genStreamWithSourceStream as one valued GPU join
+    (hsg_join_create_valued). fields1 / fields2: the numeric fields of each
+    stream's value the rest of the query reads, each a name or (name,
+    is_float). Returns (processing.JoinedStream, the joined column names
+    "s1.f" ..., "s2.g" ...): gen_select_node / gen_group_by_node are then given
+    those names as their fields, and JoinedStream.process_into hands every
+    drained batch to their op on the device."""
+    _check_join(frm)
+    before, after = windows if windows is not None else gen_join_windows(frm)
+    js = P.joinStream(engine, frm.s1, frm.s2, frm.f1, frm.f2, fields1, fields2, before, after, batch_capacity)
+    return js, js.names

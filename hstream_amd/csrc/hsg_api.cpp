@@ -242,29 +242,39 @@ static int value_ins_type(const hsg_where_ins &in, const int32_t *col_types, int
   return pops;
 }
 
-// (`what`: "where" over the value columns, "having" over the aggregate outputs)
-static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_t n, const int32_t *col_types,
-                      int32_t n_cols, int32_t max_cols, std::string &err) {
-  if (!prog) return fail(err, HSG_E_INVALID, what + ": null program");
-  if (n < 1 || n > HSG_WHERE_MAX_INS)
-    return fail(err, HSG_E_INVALID, what + ": program length " + std::to_string(n) + " outside 1.." +
-                                        std::to_string(HSG_WHERE_MAX_INS));
-  if (n_cols < 0 || n_cols > max_cols || (n_cols > 0 && !col_types))
-    return fail(err, HSG_E_INVALID, what + ": bad value columns (max " + std::to_string(max_cols) + ")");
+// What a compiler needs of a program beside its result (prog_walk).
+struct ProgFacts {
+  int fn_class = 0;       // prog_fn_class
+  // a function can give the error value or a literal-form bit of its own
+  // (MapPlan::fn_valid): any but ABS / CEIL / FLOOR / ROUND / SIGN of an i64,
+  // which is total and clears or keeps the bit
+  bool fn_valid = false;
+};
+
+// The static walk of a program's stack, written once for every checker and
+// compiler: each instruction's operands are there, values where values are
+// wanted and bools where bools are, and the program leaves one result, a bool
+// (want_bool: a predicate; the comparisons and connectives are then
+// instructions too) or a value, whose type res_f64 takes. `pre` opens every
+// message: "where: ", "having: ", "map: expr j: ". facts may be null.
+static int prog_walk(const std::string &pre, bool want_bool, const hsg_where_ins *prog, int32_t n,
+                     const int32_t *col_types, int32_t n_cols, bool &res_f64, std::string &err,
+                     ProgFacts *facts = nullptr) {
   enum { K_VALUE = 0, K_BOOL = 1 };
   int kind[HSG_WHERE_MAX_DEPTH];
   bool is_f64[HSG_WHERE_MAX_DEPTH];  // a value's static type, as the device carries it (hsg_pred.h)
   int depth = 0;
-  auto at = [&](int pc) { return what + ": instruction " + std::to_string(pc) + ": "; };
+  auto at = [&](int pc) { return pre + "instruction " + std::to_string(pc) + ": "; };
   for (int pc = 0; pc < n; ++pc) {
     const hsg_where_ins &in = prog[pc];
-    int pops = 0, want = K_VALUE, gives = K_VALUE;
+    int want = K_VALUE, gives = K_VALUE;
     bool f64 = false;
     std::string msg;
-    const int vp = value_ins_type(in, col_types, n_cols, is_f64, depth, f64, msg);
-    if (vp == -2) return fail(err, HSG_E_INVALID, at(pc) + msg);
-    if (vp >= 0) pops = vp;
-    else switch (in.op) {
+    int pops = value_ins_type(in, col_types, n_cols, is_f64, depth, f64, msg);
+    if (pops == -2) return fail(err, HSG_E_INVALID, at(pc) + msg);
+    if (pops == -1 && !want_bool)
+      return fail(err, HSG_E_INVALID, at(pc) + "opcode " + std::to_string(in.op) + " is not a value instruction");
+    if (pops == -1) switch (in.op) {
       case HSG_W_EQ: case HSG_W_NE: case HSG_W_LT: case HSG_W_GT: case HSG_W_LE: case HSG_W_GE:
         pops = 2, gives = K_BOOL;
         break;
@@ -278,6 +288,10 @@ static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_
       if (kind[depth - 1 - k] != want)
         return fail(err, HSG_E_INVALID,
                     at(pc) + (want == K_VALUE ? "a bool used as a value" : "a value used as a bool"));
+    if (facts && in.op == HSG_W_FN) {
+      facts->fn_class = std::max(facts->fn_class, fn_exact(in.arg) ? 1 : 2);
+      facts->fn_valid |= is_f64[depth - 1] || in.arg == HSG_FN_SQRT || !fn_exact(in.arg);
+    }
     depth -= pops;
     if (depth >= HSG_WHERE_MAX_DEPTH)
       return fail(err, HSG_E_INVALID, at(pc) + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
@@ -285,11 +299,26 @@ static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_
     kind[depth++] = gives;
   }
   if (depth != 1)
-    return fail(err, HSG_E_INVALID, what + ": " + std::to_string(depth) + " results left on the stack, not one");
-  if (kind[0] != K_BOOL)
     return fail(err, HSG_E_INVALID,
-                what + ": the program leaves a value, not a bool (" + (is_f64[0] ? "an f64" : "an i64") + " value)");
+                pre + std::to_string(depth) + (want_bool ? " results" : " values") + " left on the stack, not one");
+  if (want_bool && kind[0] != K_BOOL)
+    return fail(err, HSG_E_INVALID,
+                pre + "the program leaves a value, not a bool (" + (is_f64[0] ? "an f64" : "an i64") + " value)");
+  res_f64 = is_f64[0];
   return HSG_OK;
+}
+
+// (`what`: "where" over the value columns, "having" over the aggregate outputs)
+static int prog_check(const std::string &what, const hsg_where_ins *prog, int32_t n, const int32_t *col_types,
+                      int32_t n_cols, int32_t max_cols, std::string &err) {
+  if (!prog) return fail(err, HSG_E_INVALID, what + ": null program");
+  if (n < 1 || n > HSG_WHERE_MAX_INS)
+    return fail(err, HSG_E_INVALID, what + ": program length " + std::to_string(n) + " outside 1.." +
+                                        std::to_string(HSG_WHERE_MAX_INS));
+  if (n_cols < 0 || n_cols > max_cols || (n_cols > 0 && !col_types))
+    return fail(err, HSG_E_INVALID, what + ": bad value columns (max " + std::to_string(max_cols) + ")");
+  bool res_f64;
+  return prog_walk(what + ": ", true, prog, n, col_types, n_cols, res_f64, err);
 }
 
 int where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, std::string &err) {
@@ -349,46 +378,12 @@ int map_check(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_typ
     if (total > HSG_MAP_MAX_INS)
       return fail(err, HSG_E_INVALID, what + std::to_string(total) + " instructions with the expressions before it, more than " +
                                           std::to_string(HSG_MAP_MAX_INS));
-    bool is_f64[HSG_WHERE_MAX_DEPTH];  // a value's static type, as the device carries it (hsg_pred.h)
-    int depth = 0;
-    for (int pc = 0; pc < x.n; ++pc) {
-      const hsg_where_ins &in = x.prog[pc];
-      const std::string at = what + "instruction " + std::to_string(pc) + ": ";
-      bool f64 = false;
-      std::string msg;
-      const int pops = value_ins_type(in, col_types, n_cols, is_f64, depth, f64, msg);
-      if (pops == -2) return fail(err, HSG_E_INVALID, at + msg);
-      if (pops == -1)
-        return fail(err, HSG_E_INVALID, at + "opcode " + std::to_string(in.op) + " is not a value instruction");
-      if (depth < pops) return fail(err, HSG_E_INVALID, at + "stack underflow");
-      depth -= pops;
-      if (depth >= HSG_WHERE_MAX_DEPTH)
-        return fail(err, HSG_E_INVALID, at + "stack deeper than " + std::to_string(HSG_WHERE_MAX_DEPTH));
-      is_f64[depth++] = f64;
-    }
-    if (depth != 1)
-      return fail(err, HSG_E_INVALID, what + std::to_string(depth) + " values left on the stack, not one");
-    if (out_types) out_types[j] = is_f64[0] ? HSG_F64 : HSG_I64;
+    bool res_f64;
+    const int rc = prog_walk(what, false, x.prog, x.n, col_types, n_cols, res_f64, err);
+    if (rc != HSG_OK) return rc;
+    if (out_types) out_types[j] = res_f64 ? HSG_F64 : HSG_I64;
   }
   return HSG_OK;
-}
-
-// An expression (checked) holds a function that can give the error value or a
-// literal-form bit of its own (MapPlan::fn_valid): any but ABS / CEIL / FLOOR
-// / ROUND / SIGN of an i64, which is total and clears or keeps the bit.
-static bool fn_needs_valid(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols) {
-  bool is_f64[HSG_WHERE_MAX_DEPTH];
-  int depth = 0;
-  for (int pc = 0; pc < n; ++pc) {
-    bool f64 = false;
-    std::string msg;
-    const bool operand_f64 = depth > 0 && is_f64[depth - 1];
-    const int pops = value_ins_type(prog[pc], col_types, n_cols, is_f64, depth, f64, msg);
-    if (prog[pc].op == HSG_W_FN && (operand_f64 || prog[pc].arg == HSG_FN_SQRT || !fn_exact(prog[pc].arg))) return true;
-    depth -= pops;
-    is_f64[depth++] = f64;
-  }
-  return false;
 }
 
 void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_types, int32_t n_cols, bool forms,
@@ -415,8 +410,12 @@ void map_compile(const hsg_map_expr *exprs, int32_t n_exprs, const int32_t *col_
       if (in.op == HSG_W_COL) plan.reads[j] |= 1u << in.arg;
       if (in.op == HSG_W_F64 && in.imm.f != __builtin_trunc(in.imm.f)) plan.const_form[j] = true;
     }
-    plan.fn_class = std::max(plan.fn_class, (int32_t)prog_fn_class(x.prog, x.n));
-    plan.fn_valid[j] = fn_needs_valid(x.prog, x.n, col_types, n_cols);
+    ProgFacts facts;
+    bool res_f64;
+    std::string ignored;  // (checked)
+    prog_walk("", false, x.prog, x.n, col_types, n_cols, res_f64, ignored, &facts);
+    plan.fn_class = std::max(plan.fn_class, (int32_t)facts.fn_class);
+    plan.fn_valid[j] = facts.fn_valid;
     if (alias && !strict) continue;  // the caller's column as it is: nothing to run
     for (int pc = 0; pc < x.n; ++pc) {
       hsg_where_ins in = x.prog[pc];
@@ -455,8 +454,8 @@ int select_check(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr
 }
 
 int select_compile(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
-                   const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols, bool forms,
-                   SelectProg &out) {
+                   const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols,
+                   const int32_t *expr_types, bool forms, SelectProg &out) {
   memset(&out, 0, sizeof(out));
   WhereProg wp;
   memset(&wp, 0, sizeof(wp));
@@ -469,15 +468,12 @@ int select_compile(const hsg_where_ins *where, int32_t n_where, const hsg_map_ex
   }
   MapPlan plan;
   map_compile(strict, n_exprs, col_types, n_cols, forms, wp, out.m, plan);
-  int32_t types[HSG_MAP_MAX_EXPRS] = {};
-  std::string ignored;
-  if (n_exprs) map_check(exprs, n_exprs, col_types, n_cols, types, ignored);
   out.n_exprs = n_exprs;
   for (int j = 0; j < n_exprs; ++j)
-    if (types[j] == HSG_F64) out.ef64 |= 1u << j;
+    if (expr_types[j] == HSG_F64) out.ef64 |= 1u << j;
   int fc = plan.fn_class;
   if (n_having) {
-    where_compile(having, n_having, types, n_exprs, out.having);
+    where_compile(having, n_having, expr_types, n_exprs, out.having);
     fc = std::max(fc, (int)out.having.fn_class);
   }
   return fc;
@@ -519,34 +515,12 @@ extern "C" int hsg_select_check(const hsg_where_ins *where, int32_t n_where, con
 
 extern "C" int hsg_where_check(const hsg_where_ins *prog, int32_t n, const int32_t *col_types, int32_t n_cols, char *err,
                                size_t err_len) {
-  try {
-    std::string msg;
-    const int rc = where_check(prog, n, col_types, n_cols, msg);
-    if (err && err_len) {
-      const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
-      memcpy(err, msg.data(), k);
-      err[k] = 0;
-    }
-    return rc;
-  } catch (...) {
-    return HSG_E_OOM;
-  }
+  return checked_message([&](std::string &msg) { return where_check(prog, n, col_types, n_cols, msg); }, err, err_len);
 }
 
 extern "C" int hsg_having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg, char *err,
                                 size_t err_len) {
-  try {
-    std::string msg;
-    const int rc = having_check(prog, n, cfg, msg);
-    if (err && err_len) {
-      const size_t k = msg.size() < err_len - 1 ? msg.size() : err_len - 1;
-      memcpy(err, msg.data(), k);
-      err[k] = 0;
-    }
-    return rc;
-  } catch (...) {
-    return HSG_E_OOM;
-  }
+  return checked_message([&](std::string &msg) { return having_check(prog, n, cfg, msg); }, err, err_len);
 }
 
 // ---------------------------------------------------------------------------
@@ -978,7 +952,7 @@ extern "C" int hsg_op_create_select(hsg_engine *eng, const hsg_select_config *cf
     OpDevice &d = op->dev;
     d.is_select = true;
     d.forms = forms;
-    d.sel_fc = select_compile(where, n_where, exprs, n_exprs, having, n_having, cfg->col_types, cfg->n_cols, forms, d.sel);
+    d.sel_fc = select_compile(where, n_where, exprs, n_exprs, having, n_having, cfg->col_types, cfg->n_cols, types, forms, d.sel);
     if (hipSetDevice(eng->device) != hipSuccess) { delete op; return HSG_E_DEVICE; }
     // local on a sharded engine too: no communicator, each rank filters its own slice
     rc = select_device_init(d, cfg->n_cols, cfg->col_types, n_exprs, eng->batch_cap, cfg->out_capacity, eng->err);
@@ -1379,9 +1353,9 @@ extern "C" int hsg_op_map_stats(const hsg_op *op, hsg_map_stats *out) {
   return HSG_OK;
 }
 
-extern "C" int hsg_map_grid_threads(void) { return hsg::kMapGrid * hsg::kMapThreads; }
+extern "C" int hsg_map_grid_threads(void) { return hsg::pass_grid(hsg::kPassMap, 0) * hsg::kMapThreads; }
 extern "C" int hsg_map_grid_threads_fn(int fn_class) {
-  return fn_class < 0 || fn_class > 2 ? 0 : hsg::map_grid(fn_class) * hsg::kMapThreads;
+  return fn_class < 0 || fn_class > 2 ? 0 : hsg::pass_grid(hsg::kPassMap, fn_class) * hsg::kMapThreads;
 }
 extern "C" int hsg_prog_fn_class(const hsg_where_ins *prog, int32_t n) { return hsg::prog_fn_class(prog, n); }
 

@@ -116,8 +116,6 @@ struct OpDevice {
     const uint64_t *skip = nullptr;       // device word, non-zero = the batch runs again; null: sc->scratch[32]
     bool hold_emit = false;               // the per-batch emit chain was not launched and may follow the fetch
   } hv;
-  uint64_t *hv_state = nullptr;  // ticket and tile states of the pass (grow-only; ops with a program only)
-  uint64_t hv_state_words = 0;
   bool hv_ran = false;           // the last fetch of this push found the pass's word
   uint64_t hv_kept = 0;
   // Scalar SELECT (k_select.hip): the op has no aggregation at all. op_push
@@ -127,8 +125,10 @@ struct OpDevice {
   bool is_select = false;
   SelectProg sel = {};
   int32_t sel_fc = 0;             // the kernel's function class: the maximum over the three programs
-  uint64_t *sel_state = nullptr;  // ticket and tile states (grow-only)
-  uint64_t sel_state_words = 0;
+  // ticket and tile states of the op's ordered compaction (grow-only): the
+  // HAVING pass or the select pass, an op has one of them at most
+  uint64_t *tile_state = nullptr;
+  uint64_t tile_state_words = 0;
   uint64_t sel_dropped[3] = {};   // the last push: WHERE, expression, HAVING
   uint64_t wpr = 1;             // max windows per record
   bool sql_lean = false;        // per-batch LAST / literal-form op on the SQL lean kernels (k_agg_sql.hip)

@@ -1,9 +1,8 @@
-// The predicate interpreter of the WHERE / HAVING programs (include/
-// hstream_gpu.h hsg_where_ins), device side: the operand stack, the exact
-// i64 / f64 ordering and the instruction loop. k_where.hip runs it over a
-// staged batch's value columns, k_having.hip over a changelog segment's
-// aggregate columns, and k_map.hip runs its value half (value_step) to
-// compute the derived columns; the semantics are written once, here.
+// The interpreter of the row programs (include/hstream_gpu.h hsg_where_ins),
+// device side: a record's named columns, the operand stack, the exact i64 /
+// f64 ordering, the instruction loop of a predicate and the runs of a map's
+// value programs. Every pass that runs a program per row goes through here;
+// the semantics are written once.
 //
 // The program arrives as a kernel argument, so opcodes, column numbers and the
 // value types (static: column type or constant kind) live in scalar registers
@@ -12,11 +11,11 @@
 // stays in vector registers (no scratch) -- and the three-valued logic is a
 // per-lane error bit beside each entry.
 //
-// Everything here is templated on the kernel's function class FC (hsg_where.h
-// prog_fn_class): 0 has no HSG_W_FN branch, 1 the exact family, 2 all 22
-// functions. Each kernel is instantiated per class and the host launches the
-// class of the op's program, because a branch of the interpreter costs its
-// registers whether or not it is taken.
+// Everything that interprets is templated on the kernel's function class FC
+// (hsg_where.h prog_fn_class): 0 has no HSG_W_FN branch, 1 the exact family, 2
+// all 22 functions. Each kernel is instantiated per class and the host
+// launches the class of the op's program, because a branch of the interpreter
+// costs its registers whether or not it is taken.
 #pragma once
 
 #include "hsg_where.h"
@@ -29,7 +28,7 @@ constexpr int D = HSG_WHERE_MAX_DEPTH;
 // The operand stack: v[0] is the top. Values are i64 or f64 bits, bools 0 / 1.
 // err: bit k = entry k is the error value (per lane); f: bit k = entry k is
 // f64 (uniform: derived from the program alone); form: bit k = entry k's
-// literal-form bit (per lane; only the map pass reads it).
+// literal-form bit (per lane; only run_exprs hands it on).
 struct Stack {
   uint64_t v[D];
   uint32_t err;
@@ -61,6 +60,50 @@ struct Stack {
 
 __device__ __forceinline__ double as_f64(uint64_t u) { return __builtin_bit_cast(double, u); }
 __device__ __forceinline__ uint64_t as_u64(double d) { return __builtin_bit_cast(uint64_t, d); }
+
+// Record i's named columns: cv[c] is the 8-byte word of each column `cols`
+// names (0 for the others, and for every column when the lane is past the
+// batch: !in), every load in flight before the first use. The valid-byte rule
+// lives here: bit 0 alone says present -- bit c of `absent` is its complement
+// -- bit 1 is the literal form -- bit c of `cform`, 0 unless `forms` -- and a
+// null valid array is all present. A pass that keeps no forms passes forms = 0
+// and drops cform.
+__device__ __forceinline__ void load_cols(uint32_t cols, const int64_t *const (&col)[kMaxCols],
+                                          const uint8_t *const (&valid)[kMaxCols], uint64_t i, bool in, uint32_t forms,
+                                          uint64_t (&cv)[kMaxCols], uint32_t &absent, uint32_t &cform) {
+  uint32_t vb[kMaxCols];
+#pragma unroll
+  for (int c = 0; c < kMaxCols; ++c) {
+    cv[c] = 0;
+    vb[c] = 1;
+    if ((cols >> c) & 1u) {
+      if (in) cv[c] = (uint64_t)col[c][i];
+      if (in && valid[c]) vb[c] = valid[c][i];
+    }
+  }
+  absent = 0;
+  cform = 0;
+#pragma unroll
+  for (int c = 0; c < kMaxCols; ++c) {
+    absent |= ((vb[c] & 1u) ^ 1u) << c;
+    cform |= ((vb[c] >> 1) & 1u) << c;
+  }
+  if (!forms) cform = 0;
+}
+
+// Bit c: word c is an f64 (bit c of `f64cols`) that is NaN. Ahead of a HAVING
+// program that is the error value: an aggregate or an expression that has no
+// number (AVG of no value) is stored as NaN.
+template <int NC>
+__device__ __forceinline__ uint32_t nan_mask(const uint64_t (&w)[NC], uint32_t f64cols) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const double d = as_f64(w[c]);
+    if ((f64cols >> c) & 1u) m |= d != d ? 1u << c : 0u;
+  }
+  return m;
+}
 
 // Ordering of two values as Scientific orders them: -1 / 0 / 1, 2 = unordered
 // (a NaN, which no JSON number is). An i64 against an f64 is compared exactly:
@@ -200,6 +243,26 @@ __device__ __forceinline__ bool value_step(Stack &st, const hsg_where_ins &in, u
     return false;
   }
   return true;
+}
+
+// A map's value programs over one row (cv, absent, cform: load_cols), one run
+// after the other on one stack: run r is ins[end[r - 1] .. end[r]) and leaves
+// one value, the top of the stack, which at_end(r, value, err, form) takes --
+// err and form are 0 / 1, that value's error and derived literal-form bit.
+template <int FC, class F>
+__device__ __forceinline__ void run_exprs(const MapProg &p, const uint64_t (&cv)[kMaxCols], uint32_t absent,
+                                          uint32_t cform, F &&at_end) {
+  Stack st;
+  st.clear();
+  int r = 0;
+  for (int pc = 0; pc < p.n_ins; ++pc) {
+    value_step<FC>(st, p.ins[pc], p.f64, cv, absent, cform);
+    if (pc + 1 == p.end[r]) {
+      at_end(r, st.v[0], st.err & 1u, st.form & 1u);
+      st.pop();
+      ++r;
+    }
+  }
 }
 
 // One row through the program (cv, absent: value_step). True = the row is

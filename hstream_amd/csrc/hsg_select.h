@@ -12,14 +12,6 @@ namespace hsg {
 
 // Records of one tile (hsg_select_tile_rows): one record per thread.
 constexpr int kSelectTile = 256;
-// Workgroups per CU of one resident round of k_select<0> / <1> / <2>, from the
-// kernels' register counts (k_select.hip header).
-constexpr int kSelectGroupsFn0 = 4;
-constexpr int kSelectGroupsFn1 = 4;
-constexpr int kSelectGroupsFn2 = 2;
-constexpr int select_grid(int fn_class) {
-  return 256 * (fn_class == 0 ? kSelectGroupsFn0 : (fn_class == 1 ? kSelectGroupsFn1 : kSelectGroupsFn2));
-}
 
 // DevScalars::scratch words of the pass, per batch (the clears zero them; no
 // other kernel runs on a select op's scalars):
@@ -57,19 +49,17 @@ struct SelectArgs {
 };
 static_assert(sizeof(SelectProg) + sizeof(SelectArgs) <= 4096, "kernel arguments");
 
-// words of SelectArgs::state for a batch of n records
-inline uint64_t select_state_words(uint64_t n) { return ((n / kSelectTile + 1 + 2) + 1) & ~1ull; }
-
 // Type-check the three programs (hsg_select_check): HSG_OK with the
 // expressions' static types in out_types (may be null), or HSG_E_INVALID with
 // err set ("where: ", "select: " / "map: expr j: ", "having: ").
 int select_check(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
                  const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols,
                  int32_t *out_types, std::string &err);
-// (checked programs) -> SelectProg; returns the kernel's function class
+// (checked programs, expr_types as select_check left them) -> SelectProg;
+// returns the kernel's function class
 int select_compile(const hsg_where_ins *where, int32_t n_where, const hsg_map_expr *exprs, int32_t n_exprs,
-                   const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols, bool forms,
-                   SelectProg &out);
+                   const hsg_where_ins *having, int32_t n_having, const int32_t *col_types, int32_t n_cols,
+                   const int32_t *expr_types, bool forms, SelectProg &out);
 void launch_select(hipStream_t s, const SelectProg &p, const SelectArgs &a, int fn_class);
 
 }  // namespace hsg

@@ -1,11 +1,11 @@
-// WHERE / HAVING pushdown: the predicate program of include/hstream_gpu.h
-// (hsg_where_ins) as the host checks it (hsg_api.cpp where_check /
-// having_check) and as k_where.hip interprets it over a staged batch and
-// k_having.hip over a changelog segment (the interpreter itself: hsg_pred.h).
-// Not part of the ABI.
+// The row programs of include/hstream_gpu.h (hsg_where_ins) as the host checks
+// and compiles them (hsg_api.cpp) and as the passes take them: the WHERE
+// filter, the computed columns and the HAVING filter, with how each pass is
+// launched (the interpreter itself: hsg_pred.h). Not part of the ABI.
 #pragma once
 
 #include <string>
+#include <type_traits>
 
 #include "hsg_internal.h"
 
@@ -46,11 +46,36 @@ void where_compile(const hsg_where_ins *prog, int32_t n, const int32_t *col_type
 // exact family only (ABS, CEIL, FLOOR, ROUND, SIGN, SQRT), 2 any other.
 int prog_fn_class(const hsg_where_ins *prog, int32_t n);
 
-// workgroups per CU of one resident round of k_where<1> / k_where<2>, from
-// their reported occupancy: class 1 fits 7 and takes 6 as class
-// 0 does (k_where.hip launch_where), class 2 fits 2
-constexpr int kWhereGroupsFn1 = 6;
-constexpr int kWhereGroupsFn2 = 2;
+// ---- launching a pass ----------------------------------------------------------
+// Every pass that interprets a program is one kernel template over the
+// function class (hsg_pred.h), launched as one resident round of workgroups: a
+// grid past what is resident runs a second, mostly empty round, and a smaller
+// one also keeps the per-wave atomics few. Workgroups of 256 threads per CU,
+// by pass and function class, from the kernels' reported occupancy (the table
+// of DESIGN.md 5): k_where fits 7 in classes 0 and 1 and takes 6; k_having's
+// classes 0 and 1 are bound by LDS, every other entry by registers.
+enum Pass { kPassWhere, kPassMap, kPassHaving, kPassSelect };
+constexpr int kCUs = 256;
+constexpr int kGroupsPerCU[4][3] = {
+    /* k_where  */ {6, 6, 2},
+    /* k_map    */ {7, 7, 2},
+    /* k_having */ {3, 3, 2},
+    /* k_select */ {4, 4, 2},
+};
+constexpr int pass_grid(Pass pass, int fn_class) { return kCUs * kGroupsPerCU[pass][fn_class]; }
+
+// launch(fc, grid) with fc an integral constant of fn_class, so the caller
+// names its kernel template once: k<decltype(fc)::value>. grid is `groups`
+// (the workgroups the work would fill) capped to the pass's resident round.
+template <class F>
+inline void launch_by_class(Pass pass, int fn_class, uint64_t groups, F &&launch) {
+  const uint64_t cap = (uint64_t)pass_grid(pass, fn_class);
+  const dim3 grid((unsigned)(groups < cap ? groups : cap));
+  if (fn_class == 0) launch(std::integral_constant<int, 0>(), grid);
+  else if (fn_class == 1) launch(std::integral_constant<int, 1>(), grid);
+  else launch(std::integral_constant<int, 2>(), grid);
+}
+
 void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a, int fn_class);
 
 // ---- computed columns (k_map.hip) ---------------------------------------------
@@ -60,19 +85,9 @@ void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a, int fn_
 // here only when it is strict, for its error bit. The op's WHERE program, if
 // any, travels in the same argument and runs first.
 constexpr int kMapThreads = 256;
-// one resident round of workgroups: kMapGroupsPerCU per CU of 256 CUs, from
-// the kernel's reported occupancy
-constexpr int kMapGroupsPerCU = 7;
-constexpr int kMapGrid = 256 * kMapGroupsPerCU;
-// ... of k_map<1> / k_map<2>, the function classes, from theirs
-constexpr int kMapGroupsFn1 = 7;
-constexpr int kMapGroupsFn2 = 2;
-constexpr int map_grid(int fn_class) {
-  return fn_class == 0 ? kMapGrid : 256 * (fn_class == 1 ? kMapGroupsFn1 : kMapGroupsFn2);
-}
 
 struct MapProg {
-  WhereProg where;                     // where.n == 0: no filter; where.cols / f64 as k_where reads them
+  WhereProg where;                     // where.n == 0: no filter
   int32_t n_ins;                       // instructions of all runs together
   int32_t n_runs;                      // expressions evaluated
   uint32_t cols;                       // bit c: WHERE or an expression names column c
@@ -170,11 +185,9 @@ int having_check(const hsg_where_ins *prog, int32_t n, const hsg_op_config *cfg,
 // the value type of each aggregate output: COUNT_ALL / COUNT i64, AVG f64, else the column's
 void having_types(const hsg_op_config *cfg, int32_t *types);
 
-// words of HavingArgs::state for a segment of up to `rows` rows
-inline uint64_t having_state_words(uint64_t rows) { return ((rows / kHavingTile + 1 + 2) + 1) & ~1ull; }
-// workgroups per CU of one resident round of k_having<1> / k_having<2> (class 0: 3, by LDS)
-constexpr int kHavingGroupsFn1 = 3;
-constexpr int kHavingGroupsFn2 = 2;
+// words of an ordered compaction's state (HavingArgs::state, SelectArgs::state)
+// for up to `rows` rows in tiles of `tile`: the ticket, a pad, one per tile
+inline uint64_t tile_state_words(uint64_t rows, int tile) { return ((rows / tile + 1 + 2) + 1) & ~1ull; }
 void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a, int fn_class);
 
 }  // namespace hsg

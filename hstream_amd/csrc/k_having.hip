@@ -5,13 +5,13 @@
 // each emitted record's aggregate object. Here that is one pass at the end of
 // a push over the segment [base, base + rows) of the op's changelog columns:
 // the op's postfix program (include/hstream_gpu.h hsg_where_ins, interpreted
-// by hsg_pred.h exactly as k_where.hip does) runs per row over the aggregate
+// by hsg_pred.h) runs per row over the aggregate
 // columns it names, and the rows it keeps are compacted, in order, towards
 // `base` -- every column: key, window start / end, src_index, each aggregate
 // and the literal forms where kept.
 //
-// In place, one launch, a chained scan with look-back over tiles of
-// kHavingTile rows (one row per thread). A workgroup takes a tile ticket (tiles
+// In place, one launch, a chained scan with look-back (hsg_lookback.h) over
+// tiles of kHavingTile rows (one row per thread). A workgroup takes a tile ticket (tiles
 // are handed out in order, so a tile only ever waits for tiles already taken),
 // reads the named columns, evaluates, ranks its kept rows (wave ballots, a
 // scan of the wave counts in LDS), loads the other columns of the kept rows
@@ -36,8 +36,9 @@
 //   read    28 + f + 8 (a - c)       kept rows only (key, ws, we, src, the rest)
 //   written 28 + f + 8 a             kept rows only
 // plus 8 B of tile state per 256 rows each way and one ticket atomic per tile.
-// Flags: none are stored (a row's keep bit lives in a ballot). LDS: 40 KiB per
-// workgroup (256 rows of 160 B), three workgroups per CU.
+// Flags: none are stored (a row's keep bit lives in a ballot). LDS: 256 whole
+// rows of 160 B per workgroup, which is what bounds the resident round of
+// classes 0 and 1 (hsg_where.h kGroupsPerCU; the compiler's report: DESIGN.md 5).
 #include "hsg_lookback.h"
 #include "hsg_pred.h"
 
@@ -46,8 +47,7 @@ namespace hsg {
 namespace {
 
 constexpr int T = kHavingTile;
-constexpr int kWaves = T / 64;
-using namespace lookback;  // the tile states and look_back (shared with k_select.hip)
+using namespace lookback;
 
 }  // namespace
 
@@ -56,8 +56,7 @@ template <int FC>
 __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArgs a) {
   __shared__ uint64_t s_w[3 + kMaxAggs][T];  // ws, we, src, aggregates
   __shared__ uint32_t s_key[T], s_form[T];
-  __shared__ uint32_t s_wcnt[kWaves];
-  __shared__ uint64_t s_tile, s_excl;
+  __shared__ TileLds<T / 64> s_lds;
 
   uint64_t total = a.host_total;
   if (total == UINT64_MAX) total = *a.tot_a + (a.tot_b ? *a.tot_b : 0);
@@ -81,13 +80,10 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
     return;
   }
   const uint64_t n_tiles = (total + T - 1) / T;
-  uint64_t *ticket = a.state, *tiles = a.state + 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
 
   while (true) {
-    if (tid == 0) s_tile = atomicAdd((unsigned long long *)ticket, 1ull);
-    __syncthreads();
-    const uint64_t t = s_tile;
+    const uint64_t t = take_tile(s_lds, a.state);
     if (t >= n_tiles) return;
     const uint64_t row = t * T + tid;
     const bool in = row < total;
@@ -95,28 +91,12 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
 
     // the named aggregate words, all loads in flight before the program runs
     uint64_t cv[kMaxAggs];
-    uint32_t absent = 0;
 #pragma unroll
     for (int c = 0; c < kMaxAggs; ++c) cv[c] = (in && ((p.cols >> c) & 1u)) ? (uint64_t)a.out.agg[c][src] : 0;
     // an f64 output that is NaN (AVG of no value) is the error value
-#pragma unroll
-    for (int c = 0; c < kMaxAggs; ++c) {
-      const double d = pred::as_f64(cv[c]);
-      if (((p.cols & p.f64) >> c) & 1u) absent |= d != d ? 1u << c : 0u;
-    }
-    const bool keep = in && pred::eval<FC>(p, cv, absent);
-
-    // rank among the tile's kept rows
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) s_wcnt[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0, count = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      before += w < wave ? s_wcnt[w] : 0;
-      count += s_wcnt[w];
-    }
-    const uint32_t r = before + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    const bool keep = in && pred::eval<FC>(p, cv, pred::nan_mask(cv, p.cols & p.f64));
+    const Rank k = rank_kept(s_lds, keep);
+    const uint32_t r = k.rank, count = k.count;
 
     // the kept rows, whole, into LDS at their ranks: every load of the other
     // columns in flight first, then the LDS stores
@@ -139,23 +119,13 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
     // every load of the tile's rows has landed (the LDS stores consumed them)
     __syncthreads();
 
-    if (wave == 0) {
-      if (lane == 0) st_store(tiles + t, kStAgg | count);
-      const uint64_t excl = look_back(tiles, t, a.sc, ERR_HAVING);
-      if (lane == 0) {
-        s_excl = excl;
-        if (excl != kNoSum) {
-          st_store(tiles + t, kStSum | (excl + count));
-          if (t == n_tiles - 1) a.sc->scratch[kHavingWord] = kHavingRan | (excl + count);
-        }
-      }
-    }
-    __syncthreads();
-    if (s_excl == kNoSum) return;  // uniform
+    const uint64_t excl = publish_tile(s_lds, a.state + 2, t, n_tiles, count, a.sc, ERR_HAVING,
+                                       &a.sc->scratch[kHavingWord], kHavingRan);
+    if (excl == kNoSum) return;  // uniform
 
     // every predecessor has its rows in LDS or written: write ours
     if ((uint32_t)tid < count) {
-      const uint64_t dst = a.base + s_excl + tid;
+      const uint64_t dst = a.base + excl + tid;
       a.out.key[dst] = s_key[tid];
       a.out.ws[dst] = (int64_t)s_w[0][tid];
       a.out.we[dst] = (int64_t)s_w[1][tid];
@@ -165,22 +135,17 @@ __global__ __launch_bounds__(T) void k_having(const WhereProg p, const HavingArg
         if (c < a.n_aggs) a.out.agg[c][dst] = (int64_t)s_w[3 + c][tid];
       if (a.out.form) a.out.form[dst] = s_form[tid];
     }
-    __syncthreads();  // LDS and s_tile are reused by the next tile
+    __syncthreads();  // the rows' LDS and s_lds are reused by the next tile
   }
 }
 
 void launch_having(hipStream_t s, const WhereProg &p, const HavingArgs &a, int fn_class) {
   if (!p.n || !a.max_rows) return;
-  // a workgroup per tile of the host's bound, at most one resident round (three
-  // workgroups per CU by LDS); the workgroups take tiles until none is left, so
-  // the grid bounds nothing but the parallelism
-  uint64_t g = (a.max_rows + T - 1) / T;
-  // (the function classes: a round of their own occupancy)
-  const uint64_t cap = 256 * (uint64_t)(fn_class == 0 ? 3 : (fn_class == 1 ? kHavingGroupsFn1 : kHavingGroupsFn2));
-  if (g > cap) g = cap;
-  if (fn_class == 0) hipLaunchKernelGGL(k_having<0>, dim3((unsigned)g), dim3(T), 0, s, p, a);
-  else if (fn_class == 1) hipLaunchKernelGGL(k_having<1>, dim3((unsigned)g), dim3(T), 0, s, p, a);
-  else hipLaunchKernelGGL(k_having<2>, dim3((unsigned)g), dim3(T), 0, s, p, a);
+  // a workgroup per tile of the host's bound; the workgroups take tiles until
+  // none is left, so the grid bounds nothing but the parallelism
+  launch_by_class(kPassHaving, fn_class, (a.max_rows + T - 1) / T, [&](auto fc, dim3 grid) {
+    hipLaunchKernelGGL(k_having<decltype(fc)::value>, grid, dim3(T), 0, s, p, a);
+  });
 }
 
 }  // namespace hsg

@@ -8,10 +8,9 @@
 // expression, with its valid byte where one is needed, into op-owned staging;
 // the aggregation kernels then read those as the columns they always read.
 // An op with a WHERE program runs it here too, ahead of the expressions, so
-// each named column is read once: the verdict first (hsg_pred.h eval, as
-// k_where runs it), then every expression. A record the filter drops, or one
-// whose strict expression is the error value, leaves with HSG_KEY_NONE;
-// nothing is compacted.
+// each named column is read once: the verdict first (hsg_pred.h eval), then
+// every expression. A record the filter drops, or one whose strict expression
+// is the error value, leaves with HSG_KEY_NONE; nothing is compacted.
 //
 // Per record the pass moves the key in and out when it writes keys (4 + 4 B),
 // of the named columns the value and the valid byte (9 B), and per computed
@@ -19,9 +18,9 @@
 //   bytes = N * (8 * [keys written] + 9 * named columns
 //                + (8 + [valid written]) * computed outputs).
 // The programs arrive as one kernel argument and are interpreted by
-// hsg_pred.h value_step (shared with the WHERE / HAVING passes): scalar
-// opcodes, a register stack, a per-lane error bit and literal-form bit beside
-// each entry.
+// hsg_pred.h run_exprs: scalar opcodes, a register stack, a per-lane error bit
+// and literal-form bit beside each entry. The grid is one resident round
+// (hsg_where.h kGroupsPerCU; the compiler's report: DESIGN.md 5).
 #include "hsg_pred.h"
 
 namespace hsg {
@@ -37,48 +36,20 @@ __global__ __launch_bounds__(kMapThreads) void k_map(const MapProg p, const MapA
   for (uint64_t i = blockIdx.x * (uint64_t)kMapThreads + threadIdx.x; i < n_up; i += stride) {
     const bool in = i < a.n;
     const uint32_t key = in ? a.key[i] : HSG_KEY_NONE;
-    // the named columns, all loads in flight before the first instruction
     uint64_t cv[kMaxCols];
-    uint32_t vb[kMaxCols];
-#pragma unroll
-    for (int c = 0; c < kMaxCols; ++c) {
-      cv[c] = 0;
-      vb[c] = 1;
-      if ((p.cols >> c) & 1u) {
-        if (in) cv[c] = (uint64_t)a.col[c][i];
-        if (in && a.valid[c]) vb[c] = a.valid[c][i];
-      }
-    }
-    // bit 0 alone says present; bit 1 is the literal form
-    uint32_t absent = 0, cform = 0;
-#pragma unroll
-    for (int c = 0; c < kMaxCols; ++c) {
-      absent |= ((vb[c] & 1u) ^ 1u) << c;
-      cform |= ((vb[c] >> 1) & 1u) << c;
-    }
-    if (!p.forms) cform = 0;
+    uint32_t absent, cform;
+    pred::load_cols(p.cols, a.col, a.valid, i, in, p.forms, cv, absent, cform);
     const bool keep = p.where.n ? pred::eval<FC>(p.where, cv, absent) : true;
-    // the expressions, one run after the other on one stack
-    pred::Stack st;
-    st.clear();
     bool strict_err = false;
-    int r = 0;
-    for (int pc = 0; pc < p.n_ins; ++pc) {
-      pred::value_step<FC>(st, p.ins[pc], p.f64, cv, absent, cform);
-      if (pc + 1 == p.end[r]) {
-        // the run's one value is the top of the stack
-        const bool e = st.err & 1u;
-        strict_err |= e && ((p.strict >> r) & 1u);
-        const int o = p.out[r];
-        if (o >= 0 && in) {
-          a.ocol[o][i] = (int64_t)st.v[0];
-          // (absent is the whole byte 0: the aggregates take any other byte as present)
-          if (a.ovalid[o]) a.ovalid[o][i] = e ? (uint8_t)0 : (uint8_t)(1u | ((st.form & p.forms & 1u) << 1));
-        }
-        st.pop();
-        ++r;
+    pred::run_exprs<FC>(p, cv, absent, cform, [&](int r, uint64_t v, uint32_t e, uint32_t form) {
+      strict_err |= e && ((p.strict >> r) & 1u);
+      const int o = p.out[r];
+      if (o >= 0 && in) {
+        a.ocol[o][i] = (int64_t)v;
+        // (absent is the whole byte 0: the aggregates take any other byte as present)
+        if (a.ovalid[o]) a.ovalid[o][i] = e ? (uint8_t)0 : (uint8_t)(1u | ((form & p.forms) << 1));
       }
-    }
+    });
     const bool keyed = key != HSG_KEY_NONE;
     const bool w_drop = keyed && !keep;
     const bool m_drop = keyed && keep && strict_err;
@@ -98,14 +69,10 @@ __global__ __launch_bounds__(kMapThreads) void k_map(const MapProg p, const MapA
 
 void launch_map(hipStream_t s, const MapProg &p, const MapArgs &a, int fn_class) {
   if (!a.n || (!p.n_ins && !p.where.n)) return;
-  // one resident round of workgroups over the 256 CUs (kMapGroupsPerCU from
-  // the kernel's occupancy); a larger batch strides
-  uint64_t g = (a.n + kMapThreads - 1) / kMapThreads;
-  const uint64_t cap = (uint64_t)map_grid(fn_class);
-  if (g > cap) g = cap;
-  if (fn_class == 0) hipLaunchKernelGGL(k_map<0>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
-  else if (fn_class == 1) hipLaunchKernelGGL(k_map<1>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
-  else hipLaunchKernelGGL(k_map<2>, dim3((unsigned)g), dim3(kMapThreads), 0, s, p, a);
+  // a larger batch strides
+  launch_by_class(kPassMap, fn_class, (a.n + kMapThreads - 1) / kMapThreads, [&](auto fc, dim3 grid) {
+    hipLaunchKernelGGL(k_map<decltype(fc)::value>, grid, dim3(kMapThreads), 0, s, p, a);
+  });
 }
 
 }  // namespace hsg

@@ -12,9 +12,10 @@
 // Per record the pass moves the key in and out (4 + 4 B) and, of the columns
 // the program names only, the value and the valid byte (9 B):
 //   bytes = N * (8 + 9 * named columns).
-// The program arrives as a kernel argument and is interpreted by hsg_pred.h
-// (shared with the HAVING pass, k_having.hip): scalar opcodes, a register
-// stack, a per-lane error bit beside each entry.
+// The program arrives as a kernel argument and is interpreted by hsg_pred.h:
+// scalar opcodes, a register stack, a per-lane error bit beside each entry.
+// The grid is one resident round (hsg_where.h kGroupsPerCU; the compiler's
+// report: DESIGN.md 5).
 #include "hsg_pred.h"
 
 namespace hsg {
@@ -32,18 +33,10 @@ __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, cons
   for (uint64_t i = blockIdx.x * (uint64_t)kWhereThreads + threadIdx.x; i < n_up; i += stride) {
     const bool in = i < a.n;
     const uint32_t key = in ? a.key[i] : HSG_KEY_NONE;
-    // the named columns, all loads in flight before the program runs
+    // the named columns; a predicate reads no literal form
     uint64_t cv[kMaxCols];
-    uint32_t absent = 0;
-#pragma unroll
-    for (int c = 0; c < kMaxCols; ++c) {
-      cv[c] = 0;
-      if ((p.cols >> c) & 1u) {
-        if (in) cv[c] = (uint64_t)a.col[c][i];
-        // bit 0 alone says present; bit 1 is the literal form
-        if (in && a.valid[c] && !(a.valid[c][i] & 1u)) absent |= 1u << c;
-      }
-    }
+    uint32_t absent, cform;
+    pred::load_cols(p.cols, a.col, a.valid, i, in, 0u, cv, absent, cform);
     const bool keep = pred::eval<FC>(p, cv, absent);
     const bool drop = key != HSG_KEY_NONE && !keep;
     if (in) a.out[i] = drop ? HSG_KEY_NONE : key;
@@ -56,16 +49,10 @@ __global__ __launch_bounds__(kWhereThreads) void k_where(const WhereProg p, cons
 
 void launch_where(hipStream_t s, const WhereProg &p, const WhereArgs &a, int fn_class) {
   if (!a.n || !p.n) return;
-  // one resident round of workgroups: 6 per CU of 256 CUs (the kernel fits 7,
-  // 28 waves per CU; a grid past what is resident runs a second, mostly empty
-  // round), which also keeps the per-wave atomics to a few thousand
-  uint64_t g = (a.n + kWhereThreads - 1) / kWhereThreads;
-  // (the function classes: a round of their own occupancy)
-  const uint64_t cap = 256 * (uint64_t)(fn_class == 0 ? 6 : (fn_class == 1 ? kWhereGroupsFn1 : kWhereGroupsFn2));
-  if (g > cap) g = cap;
-  if (fn_class == 0) hipLaunchKernelGGL(k_where<0>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
-  else if (fn_class == 1) hipLaunchKernelGGL(k_where<1>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
-  else hipLaunchKernelGGL(k_where<2>, dim3((unsigned)g), dim3(kWhereThreads), 0, s, p, a);
+  // a larger batch strides
+  launch_by_class(kPassWhere, fn_class, (a.n + kWhereThreads - 1) / kWhereThreads, [&](auto fc, dim3 grid) {
+    hipLaunchKernelGGL(k_where<decltype(fc)::value>, grid, dim3(kWhereThreads), 0, s, p, a);
+  });
 }
 
 }  // namespace hsg

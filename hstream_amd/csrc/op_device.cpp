@@ -472,12 +472,9 @@ void op_device_free(OpDevice &d) {
   if (d.tkeys) hipFree(d.tkeys);
   d.tkeys = nullptr;
   d.tkeys_cap = 0;
-  if (d.hv_state) hipFree(d.hv_state);
-  d.hv_state = nullptr;
-  d.hv_state_words = 0;
-  if (d.sel_state) hipFree(d.sel_state);
-  d.sel_state = nullptr;
-  d.sel_state_words = 0;
+  if (d.tile_state) hipFree(d.tile_state);
+  d.tile_state = nullptr;
+  d.tile_state_words = 0;
   if (d.tj.mem) hipFree(d.tj.mem);
   d.tj.mem = nullptr;
   d.tj.cap = 0;
@@ -586,7 +583,16 @@ static int widen_batch(OpDevice &d, const hsg_batch *b, const void *k16, const v
 }
 
 static int stage_batch_raw(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set);
-static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set);
+static int stage_where(OpDevice &d, Batch &kb, std::string &err, int staged_set);
+static int stage_map(OpDevice &d, Batch &kb, std::string &err, int staged_set);
+
+// Where a pass leaves the masked keys: in place when the staged keys are the
+// op's own buffer, else in d.st_key (a caller's device-resident array is never
+// written).
+static uint32_t *masked_keys(OpDevice &d, const Batch &kb, int staged_set) {
+  const bool own = kb.key == d.st_key || (staged_set >= 0 && kb.key == d.pre[staged_set].key);
+  return own ? const_cast<uint32_t *>(kb.key) : d.st_key;
+}
 
 // Resolve the batch into device pointers, copying host arrays into staging
 // (or taking the ones op_prestage queued for it). The valid bytes go to the
@@ -596,9 +602,7 @@ static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &er
 // -- the synchronous push, prestaged asynchronous batches, the exchange's
 // send sides -- aggregates the masked batch: k_where reads the staged keys
 // and the caller's columns and leaves the key or HSG_KEY_NONE in op-owned
-// memory (in place when the staged keys are the op's own buffer, else in
-// d.st_key: a caller's device-resident array is never written). The kernels'
-// columns are then the ones an aggregate reads (OpDevice::col_map).
+// memory (masked_keys). An op with a map runs that pass here instead.
 int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
   // (a sharded push that falls back from the fast exchange stages its batch a
   // second time: the filter / the map ran, and counted, the first time)
@@ -609,14 +613,22 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
   }
   int rc = stage_batch_raw(d, b, kb, err, staged_set);
   if (rc != HSG_OK || !staged_pass) return rc;
-  if (d.map.n_exprs) return stage_map(d, b, kb, err, staged_set);
+  rc = d.map.n_exprs ? stage_map(d, kb, err, staged_set) : stage_where(d, kb, err, staged_set);
+  if (rc != HSG_OK) return rc;
+  d.where_staged = b;
+  d.where_kb = kb;
+  return HSG_OK;
+}
+
+// The op's WHERE program over the staged batch (k_where.hip); the kernels'
+// columns are then the ones an aggregate reads (OpDevice::col_map).
+static int stage_where(OpDevice &d, Batch &kb, std::string &err, int staged_set) {
   if (kb.n) {
     WhereArgs w;
     memset(&w, 0, sizeof(w));
     w.n = kb.n;
     w.key = kb.key;
-    const bool own = kb.key == d.st_key || (staged_set >= 0 && kb.key == d.pre[staged_set].key);
-    w.out = own ? const_cast<uint32_t *>(kb.key) : d.st_key;
+    w.out = masked_keys(d, kb, staged_set);
     for (int c = 0; c < d.user_cols; ++c) {
       w.col[c] = kb.col[c];
       w.valid[c] = kb.valid[c];
@@ -632,8 +644,6 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
     kb.col[c] = on ? in.col[d.col_map[c]] : nullptr;
     kb.valid[c] = on ? in.valid[d.col_map[c]] : nullptr;
   }
-  d.where_staged = b;
-  d.where_kb = kb;
   return HSG_OK;
 }
 
@@ -647,7 +657,7 @@ int stage_batch(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, in
 // expression holds a constant that is not integral, or the expression holds a
 // function that can give the error value or a form bit (MapPlan::fn_valid).
 // The kernels' column j is then expression j.
-static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &err, int staged_set) {
+static int stage_map(OpDevice &d, Batch &kb, std::string &err, int staged_set) {
   const MapPlan &m = d.map;
   bool need_valid[HSG_MAP_MAX_EXPRS] = {};
   for (int j = 0; j < m.n_exprs; ++j) {
@@ -659,10 +669,7 @@ static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &er
     memset(&a, 0, sizeof(a));
     a.n = kb.n;
     a.key = kb.key;
-    if (m.keys) {
-      const bool own = kb.key == d.st_key || (staged_set >= 0 && kb.key == d.pre[staged_set].key);
-      a.out = own ? const_cast<uint32_t *>(kb.key) : d.st_key;
-    }
+    if (m.keys) a.out = masked_keys(d, kb, staged_set);
     for (int c = 0; c < d.user_cols; ++c) {
       a.col[c] = kb.col[c];
       a.valid[c] = kb.valid[c];
@@ -690,8 +697,6 @@ static int stage_map(OpDevice &d, const hsg_batch *b, Batch &kb, std::string &er
       kb.valid[j] = need_valid[j] ? d.map_valid[m.ocol[j]] : nullptr;
     }
   }
-  d.where_staged = b;
-  d.where_kb = kb;
   return HSG_OK;
 }
 
@@ -863,6 +868,22 @@ static int status_from_err(uint32_t e, std::string &err) {
   return HSG_OK;
 }
 
+// d.tile_state with room for `words` words, the first `words` zeroed on the
+// stream ahead of the launch that takes them. Grow-only: at least 2 * 1024
+// words, otherwise twice what is asked.
+static int zeroed_tile_state(OpDevice &d, uint64_t words, std::string &err) {
+  if (words > d.tile_state_words) {
+    if (d.tile_state) hipFree(d.tile_state);
+    d.tile_state = nullptr;
+    d.tile_state_words = 0;
+    const uint64_t want = words > 2 * 1024 ? 2 * words : 2 * 1024;
+    DTRY(hipMalloc((void **)&d.tile_state, want * sizeof(uint64_t)));
+    d.tile_state_words = want;
+  }
+  DTRY(hipMemsetAsync(d.tile_state, 0, words * sizeof(uint64_t), d.stream));
+  return HSG_OK;
+}
+
 // The HAVING pass over the rows the batch appended (k_having.hip), enqueued
 // ahead of the fetch that reads the batch's scalars: no round trip of its own.
 // The rows' count is on the device (or in hv.host_total); the grid and the
@@ -872,16 +893,8 @@ static int having_pass(OpDevice &d, std::string &err) {
   uint64_t rows = d.hv.host_total != UINT64_MAX ? d.hv.host_total : d.hv.bound;
   if (rows > room) rows = room;
   if (!rows) return HSG_OK;
-  const uint64_t words = having_state_words(rows);
-  if (words > d.hv_state_words) {
-    if (d.hv_state) hipFree(d.hv_state);
-    d.hv_state = nullptr;
-    d.hv_state_words = 0;
-    const uint64_t want = words > 2 * 1024 ? 2 * words : 2 * 1024;
-    DTRY(hipMalloc((void **)&d.hv_state, want * sizeof(uint64_t)));
-    d.hv_state_words = want;
-  }
-  DTRY(hipMemsetAsync(d.hv_state, 0, words * sizeof(uint64_t), d.stream));
+  const int rc = zeroed_tile_state(d, tile_state_words(rows, kHavingTile), err);
+  if (rc != HSG_OK) return rc;
   HavingArgs h;
   memset(&h, 0, sizeof(h));
   h.out = d.out;
@@ -893,7 +906,7 @@ static int having_pass(OpDevice &d, std::string &err) {
   h.tot_b = d.hv.dev_total ? nullptr : &d.sc->scratch[3];
   h.skip = d.hv.skip ? d.hv.skip : &d.sc->scratch[32];
   h.hold_emit = d.hv.hold_emit ? 1 : 0;
-  h.state = d.hv_state;
+  h.state = d.tile_state;
   h.sc = d.sc;
   launch_having(d.stream, d.having, h, (int)d.having.fn_class);
   DTRY(hipGetLastError());
@@ -967,16 +980,8 @@ static int push_select(OpDevice &d, const PushArgs &a, const Batch &kb, PushResu
   int rc = clear_batch_scalars(d, err);
   if (rc != HSG_OK) return rc;
   if (kb.n) {
-    const uint64_t words = select_state_words(kb.n);
-    if (words > d.sel_state_words) {
-      if (d.sel_state) hipFree(d.sel_state);
-      d.sel_state = nullptr;
-      d.sel_state_words = 0;
-      const uint64_t want = words > 2 * 1024 ? 2 * words : 2 * 1024;
-      DTRY(hipMalloc((void **)&d.sel_state, want * sizeof(uint64_t)));
-      d.sel_state_words = want;
-    }
-    DTRY(hipMemsetAsync(d.sel_state, 0, words * sizeof(uint64_t), d.stream));
+    rc = zeroed_tile_state(d, tile_state_words(kb.n, kSelectTile), err);
+    if (rc != HSG_OK) return rc;
     SelectArgs s;
     memset(&s, 0, sizeof(s));
     s.n = kb.n;
@@ -989,7 +994,7 @@ static int push_select(OpDevice &d, const PushArgs &a, const Batch &kb, PushResu
     s.out = d.out;
     s.base = a.pending;
     s.rec_base = a.rec_base;
-    s.state = d.sel_state;
+    s.state = d.tile_state;
     s.sc = d.sc;
     DTRY(hipEventRecord(d.ev_a, d.stream));
     launch_select(d.stream, d.sel, s, d.sel_fc);

@@ -433,7 +433,19 @@ INGEST_SYMBOLS = [
     "hsg_decode_json_batch",
     "hsg_decode_json",
     "hsg_decode_json_spelled",
+    "hsg_gpu_decoder_create",
+    "hsg_gpu_decode_json",
+    "hsg_gpu_decoder_fetch",
+    "hsg_gpu_decoder_destroy",
+    "hsg_gpu_decoder_last_error",
+    "hsg_json_fast_probe",
 ]
+
+# device decode limits (hstream_ingest.h "GPU ingest")
+HSG_GPU_DEC_MAX_RECORD = 4096
+HSG_GPU_DEC_MAX_KEY = 48
+HSG_GPU_DEC_MAX_COLS = 8
+HSG_GPU_DEC_MAX_NAME = 64
 
 HSG_SPELL_ALT = 0x80000000
 
@@ -454,6 +466,33 @@ class hsg_decoder_config(C.Structure):
         ("col_types", C.POINTER(C.c_int32)),
         ("col_numeric", C.POINTER(C.c_uint8)),
         ("literal_forms", C.c_int32),
+    ]
+
+
+class hsg_gpu_decode_stats(C.Structure):
+    _fields_ = [
+        ("records", C.c_uint64),
+        ("accepted", C.c_uint64),
+        ("host_records", C.c_uint64),
+        ("new_keys", C.c_uint64),
+        ("table_slots", C.c_uint64),
+        ("table_rebuilds", C.c_uint64),
+    ]
+
+
+class hsg_json_probe(C.Structure):
+    _fields_ = [
+        ("accept", C.c_int32),
+        ("key_tag", C.c_int32),
+        ("key_neg", C.c_int32),
+        ("key_e", C.c_int32),
+        ("key_m", C.c_uint64),
+        ("key_off", C.c_uint32),
+        ("key_len", C.c_uint32),
+        ("key_int_form", C.c_int32),
+        ("reserved", C.c_int32),
+        ("words", C.c_uint64 * 8),
+        ("valid", C.c_uint8 * 8),
     ]
 
 

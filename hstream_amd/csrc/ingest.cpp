@@ -1087,6 +1087,16 @@ void keydict_alt_texts(const hsg_keydict *d, const char **text, const uint64_t *
   *off = d->alt_off.data();
   *n = d->alt_off.size() - 1;
 }
+// For the device key table (gpu_ingest.cpp): the keys' canonical bytes and the
+// forms of their first spellings, id after id.
+void keydict_canon(const hsg_keydict *d, const char **canon, const uint64_t **coff, const char **form,
+                   const uint64_t **foff, uint64_t *n) {
+  *canon = d->canon.data();
+  *coff = d->coff.data();
+  *form = d->form.data();
+  *foff = d->foff.data();
+  *n = d->size();
+}
 // For the sink encoder (sink.cpp): the key texts, id after id.
 void keydict_texts(const hsg_keydict *d, const char **text, const uint64_t **off, uint64_t *n) {
   *text = d->text.data();

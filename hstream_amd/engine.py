@@ -341,6 +341,12 @@ class GpuOp(OpHandle):
         The arrays are kept alive until the completion has run."""
         from .columnar import make_batch
         b, keep = make_batch(key_id, ts, cols, valid, mem, **enc)
+        return self.push_batch_async(b, watermark, done, keep)
+
+    def push_batch_async(self, batch, watermark=None, done=None, keep=None):
+        """hsg_push_batch_async of a ready hsg_batch (e.g. a GpuDecodedBatch's
+        device batch with its ready_event); `keep` is held until the
+        completion has run. Otherwise as push_async."""
         wm = watermark if watermark is not None else C.c_int64(-1)
         entry = {}
 
@@ -352,11 +358,11 @@ class GpuOp(OpHandle):
                 self._inflight.pop(id(entry), None)
 
         cb = abi.HSG_DONE_FN(_cb)
-        entry.update(keep=keep, b=b, cb=cb, wm=wm)
+        entry.update(keep=keep, b=batch, cb=cb, wm=wm)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
         self._inflight[id(entry)] = entry
-        rc = self._lib.hsg_push_batch_async(self._h, C.byref(b), C.byref(wm), cb, None)
+        rc = self._lib.hsg_push_batch_async(self._h, C.byref(batch), C.byref(wm), cb, None)
         if rc != abi.HSG_OK:
             self._inflight.pop(id(entry), None)
         self._check(rc, "push_batch_async")

@@ -51,6 +51,20 @@ def _lib():
         L.hsg_batch_narrow.restype = C.c_int
         L.hsg_keydict_spelling_text.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, P(C.c_size_t)]
         L.hsg_keydict_spelling_text.restype = C.c_int
+        L.hsg_gpu_decoder_create.argtypes = [vp, P(abi.hsg_decoder_config), vp, C.c_uint64, C.c_uint64, C.c_uint64,
+                                             P(vp)]
+        L.hsg_gpu_decoder_create.restype = C.c_int
+        L.hsg_gpu_decode_json.argtypes = [vp, C.c_uint64, vp, vp, vp, P(abi.hsg_batch), vp, P(C.c_uint64), C.c_int,
+                                          P(abi.hsg_sink_spellings), P(abi.hsg_gpu_decode_stats), C.c_int]
+        L.hsg_gpu_decode_json.restype = C.c_int
+        L.hsg_gpu_decoder_fetch.argtypes = [vp, P(abi.hsg_batch), P(abi.hsg_sink_spellings), vp, vp, P(vp), P(vp), vp]
+        L.hsg_gpu_decoder_fetch.restype = C.c_int
+        L.hsg_gpu_decoder_destroy.argtypes = [vp]
+        L.hsg_gpu_decoder_destroy.restype = None
+        L.hsg_gpu_decoder_last_error.argtypes = [vp]
+        L.hsg_gpu_decoder_last_error.restype = C.c_char_p
+        L.hsg_json_fast_probe.argtypes = [P(abi.hsg_decoder_config), vp, C.c_uint64, P(abi.hsg_json_probe)]
+        L.hsg_json_fast_probe.restype = C.c_int
         _declared = True
     return L
 
@@ -234,6 +248,137 @@ class Decoder:
     def close(self):
         if self._h:
             self._L.hsg_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _decoder_config(key_field, cols, literal_forms):
+    """(hsg_decoder_config, the arrays it points into)."""
+    n = len(cols)
+    fields = (C.c_char_p * max(1, n))(*[f.encode() for f, _, _ in cols])
+    types = (C.c_int32 * max(1, n))(*[t for _, t, _ in cols])
+    num = (C.c_uint8 * max(1, n))(*[1 if x else 0 for _, _, x in cols])
+    cfg = abi.hsg_decoder_config(key_field=key_field.encode() if key_field is not None else None, n_cols=n,
+                                 col_fields=fields, col_types=types, col_numeric=num,
+                                 literal_forms=1 if literal_forms else 0)
+    return cfg, (fields, types, num)
+
+
+class FastProbe:
+    """hsg_json_fast_probe: the device decoder's scanner, compiled for the host,
+    over one record -- the key-independent part of the fast subset's verdict,
+    the column words and the key's class. Runs without a GPU."""
+
+    def __init__(self, key_field, cols: Sequence[Tuple[str, int, bool]], literal_forms: bool = False):
+        self._L = _lib()
+        self._cfg, self._keep = _decoder_config(key_field, list(cols), literal_forms)
+        out = abi.hsg_json_probe()
+        _check(self._L.hsg_json_fast_probe(C.byref(self._cfg), b"{}", 2, C.byref(out)), "hsg_json_fast_probe")
+
+    def __call__(self, rec: bytes) -> "abi.hsg_json_probe":
+        out = abi.hsg_json_probe()
+        buf = C.create_string_buffer(rec, max(1, len(rec)))
+        _check(self._L.hsg_json_fast_probe(C.byref(self._cfg), C.addressof(buf), len(rec), C.byref(out)),
+               "hsg_json_fast_probe")
+        return out
+
+
+class GpuDecodedBatch:
+    """One hsg_gpu_decode_json call: .batch is the HSG_MEM_DEVICE hsg_batch
+    (its arrays belong to the decoder and stay valid until the call after the
+    next one; ready_event is set), .status u8[n] / .rejected as the host
+    decoder's, .spellings an abi.hsg_sink_spellings over device memory or
+    None, .stats a dict of hsg_gpu_decode_stats."""
+
+    def __init__(self, dec, batch, status, rejected, spellings, stats, col_types):
+        self._dec = dec
+        self.batch, self.status, self.rejected, self.spellings = batch, status, rejected, spellings
+        self.stats, self.col_types = stats, col_types
+
+    @property
+    def n(self):
+        return int(self.batch.n)
+
+    def wait(self):
+        """Block until the batch's ready_event: the device has written it."""
+        _check(self._dec._L.hsg_gpu_decoder_fetch(self._dec._h, C.byref(self.batch), None, None, None, None, None,
+                                                  None), "hsg_gpu_decoder_fetch")
+
+    def to_host(self):
+        """(key_id, ts, cols, valid, spell or None) copied to numpy arrays,
+        after the batch's ready_event (hsg_gpu_decoder_fetch)."""
+        n, types = self.n, self.col_types
+        key, ts = np.empty(n, np.uint32), np.empty(n, np.int64)
+        cols = [np.empty(n, np.float64 if t == abi.HSG_F64 else np.int64) for t in types]
+        valid = [np.empty(n, np.uint8) for _ in types]
+        spell = np.empty(n, np.uint32) if self.spellings is not None else None
+        cp = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
+        vp = (C.c_void_p * max(1, len(valid)))(*[v.ctypes.data for v in valid])
+        rc = self._dec._L.hsg_gpu_decoder_fetch(self._dec._h, C.byref(self.batch),
+                                                C.byref(self.spellings) if self.spellings is not None else None,
+                                                key.ctypes.data, ts.ctypes.data, cp, vp,
+                                                spell.ctypes.data if spell is not None else None)
+        _check(rc, "hsg_gpu_decoder_fetch")
+        return key, ts, cols, valid, spell
+
+
+class GpuDecoder:
+    """hsg_gpu_decoder: the poll batch decoded on the device, the records
+    outside the fast subset (include/hstream_ingest.h "GPU ingest") through
+    the host decoder, with results equal to Decoder's bit for bit. cols as
+    Decoder's. Raises HStreamGpuError(HSG_E_INVALID) for a configuration the
+    device path does not take (more than 8 columns, a long or non-ASCII field
+    name): keep Decoder then."""
+
+    def __init__(self, engine, keys: "KeyDict", key_field, cols: Sequence[Tuple[str, int, bool]],
+                 literal_forms: bool = False, max_records: int = 1 << 20, max_bytes: int = 1 << 27,
+                 table_slots: int = 1 << 16):
+        self._L = _lib()
+        self.engine, self.keys = engine, keys
+        self.cols = list(cols)
+        self.max_records, self.max_bytes = int(max_records), int(max_bytes)
+        cfg, keep = _decoder_config(key_field, self.cols, literal_forms)
+        h = C.c_void_p()
+        _check(self._L.hsg_gpu_decoder_create(engine._h, C.byref(cfg), keys.handle if keys is not None else None,
+                                              int(max_records), int(max_bytes), int(table_slots), C.byref(h)),
+               "hsg_gpu_decoder_create")
+        self._h = h
+
+    def decode(self, buf: bytes, off: np.ndarray, ts: np.ndarray, threads: int = 0, spellings: bool = False,
+               base=None) -> GpuDecodedBatch:
+        """One poll batch (as Decoder.decode takes it). base: the address the
+        offsets count from, when it is not buf's own (a view into a larger
+        buffer)."""
+        n = len(off) - 1
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        ts_in = np.ascontiguousarray(ts, dtype=np.int64)
+        if base is None:
+            self._buf_keep = buf if isinstance(buf, (bytes, bytearray)) else bytes(buf)
+            base = C.cast(C.c_char_p(self._buf_keep), C.c_void_p).value if isinstance(self._buf_keep, bytes) \
+                else C.addressof(C.c_char.from_buffer(self._buf_keep))
+        out = abi.hsg_batch()
+        status = np.empty(n, np.uint8)
+        rej = C.c_uint64()
+        sp = abi.hsg_sink_spellings()
+        st = abi.hsg_gpu_decode_stats()
+        rc = self._L.hsg_gpu_decode_json(self._h, n, base, off.ctypes.data, ts_in.ctypes.data, C.byref(out),
+                                         status.ctypes.data, C.byref(rej), 1 if spellings else 0, C.byref(sp),
+                                         C.byref(st), int(threads))
+        if rc != abi.HSG_OK:
+            msg = self._L.hsg_gpu_decoder_last_error(self._h)
+            raise abi.HStreamGpuError(rc, f"hsg_gpu_decode_json: {msg.decode() if msg else ''}")
+        stats = {k: int(getattr(st, k)) for k, _ in abi.hsg_gpu_decode_stats._fields_}
+        return GpuDecodedBatch(self, out, status, int(rej.value), sp if spellings else None, stats,
+                               [t for _, t, _ in self.cols])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.hsg_gpu_decoder_destroy(self._h)
             self._h = None
 
     def __del__(self):

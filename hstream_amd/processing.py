@@ -433,19 +433,26 @@ class Table:
                 out.append((key, vals))
         return out
 
-    def process_json(self, buf: bytes, off, ts, watermark=-1, threads=0):
+    def process_json(self, buf: bytes, off, ts, watermark=-1, threads=0, device_decode=False):
         """One poll batch of raw JSON record values (SourceRecord srcValue) and
         their timestamps, decoded by the native ingest (include/hstream_ingest.h)
-        straight into the op's columns; needs Materialized(keys=ingest.KeyDict())."""
+        straight into the op's columns; needs Materialized(keys=ingest.KeyDict()).
+        device_decode: decode on the GPU (ingest.GpuDecoder; the records outside
+        its fast subset through the host decoder) and push the device batch."""
         from . import ingest
         if not isinstance(self.mat.keys, ingest.KeyDict):
             raise TypeError("process_json needs Materialized(keys=hstream_amd.ingest.KeyDict())")
-        if self._decoder is None:
-            self._decoder = ingest.Decoder(self.grouped.key_field,
-                                           [(f, abi.HSG_F64 if fl else abi.HSG_I64, num)
-                                            for (f, fl), num in zip(self.fields, self.numeric)])
-        keys, ts_out, cols, valid, _, _ = self._decoder.decode(self.mat.keys, buf, off, ts, threads)
-        wm = self.op.push(keys, ts_out, cols, valid, watermark=watermark)
+        dcols = [(f, abi.HSG_F64 if fl else abi.HSG_I64, num) for (f, fl), num in zip(self.fields, self.numeric)]
+        if device_decode:
+            self._gpu_decoder = _sized_gpu_decoder(getattr(self, "_gpu_decoder", None), self.grouped.engine,
+                                                   self.mat.keys, self.grouped.key_field, dcols, False, off)
+            db = self._gpu_decoder.decode(buf, off, ts, threads)
+            wm = self.op.push_batch(db.batch, watermark=watermark)
+        else:
+            if self._decoder is None:
+                self._decoder = ingest.Decoder(self.grouped.key_field, dcols)
+            keys, ts_out, cols, valid, _, _ = self._decoder.decode(self.mat.keys, buf, off, ts, threads)
+            wm = self.op.push(keys, ts_out, cols, valid, watermark=watermark)
         rows = self.op.drain() if self.spec.emit_mode != abi.HSG_EMIT_NONE else None
         return wm, ([] if rows is None else self._rows(rows))
 
@@ -604,17 +611,23 @@ class Stream:
         wm = self.op.push(keys, ts, cols, valid, watermark=watermark)
         return wm, self._forward(self.op.drain(), base, lambda k: records[k]["value"])
 
-    def process_json(self, buf: bytes, off, ts, watermark=-1, threads=0):
+    def process_json(self, buf: bytes, off, ts, watermark=-1, threads=0, device_decode=False):
         """One poll batch of raw JSON record values and their timestamps,
         decoded by the native ingest without a key field; a SELECT * stream
-        forwards the records' own bytes."""
+        forwards the records' own bytes. device_decode: as Table.process_json."""
         from . import ingest
-        if self._decoder is None:
-            self._decoder = ingest.Decoder(None, [(f, abi.HSG_F64 if fl else abi.HSG_I64, True) for f, fl in self.fields],
-                                           literal_forms=self.literal_forms)
-        keys, ts_out, cols, valid, _, _ = self._decoder.decode(None, buf, off, ts, threads)
+        dcols = [(f, abi.HSG_F64 if fl else abi.HSG_I64, True) for f, fl in self.fields]
         base = self.op.stats()["records"]
-        wm = self.op.push(keys, ts_out, cols, valid, watermark=watermark)
+        if device_decode:
+            self._gpu_decoder = _sized_gpu_decoder(getattr(self, "_gpu_decoder", None), self.engine, None, None, dcols,
+                                                   self.literal_forms, off)
+            db = self._gpu_decoder.decode(buf, off, ts, threads)
+            wm = self.op.push_batch(db.batch, watermark=watermark)
+        else:
+            if self._decoder is None:
+                self._decoder = ingest.Decoder(None, dcols, literal_forms=self.literal_forms)
+            keys, ts_out, cols, valid, _, _ = self._decoder.decode(None, buf, off, ts, threads)
+            wm = self.op.push(keys, ts_out, cols, valid, watermark=watermark)
         return wm, self._forward(self.op.drain(), base, lambda k: bytes(buf[int(off[k]):int(off[k + 1])]))
 
     def close(self):
@@ -703,10 +716,28 @@ def joinTable(table: Table, joiner, records) -> list:
     return join_table_result(records, rows, [a.name for a in table.aggs], joiner, kf)
 
 
-def runTask(poll, table: Table, max_polls=None, sink=None):
+def _sized_gpu_decoder(dec, engine, keys, key_field, cols, literal_forms, off):
+    """The device decoder of a process_json(device_decode=True) caller, made on
+    first use and made again, larger, when a poll batch outgrows it."""
+    from . import ingest
+    n, nbytes = len(off) - 1, int(off[-1]) - int(off[0]) if len(off) else 0
+    if dec is not None and n <= dec.max_records and nbytes <= dec.max_bytes:
+        return dec
+    max_records = max(1 << 16, 2 * n, dec.max_records if dec is not None else 0)
+    max_bytes = max(1 << 24, 2 * nbytes, dec.max_bytes if dec is not None else 0)
+    if dec is not None:
+        dec.close()
+    dec = ingest.GpuDecoder(engine, keys, key_field, cols, literal_forms=literal_forms, max_records=max_records,
+                            max_bytes=max_bytes)
+    return dec
+
+
+def runTask(poll, table: Table, max_polls=None, sink=None, device_decode=False):
     """Processor.hs:99-144 for one windowed aggregate: poll a batch, advance the
     task's stream time over every polled record, run the operator, forward
-    the changelog to `sink`. `poll()` returns a list of records or None.
+    the changelog to `sink`. `poll()` returns a list of records, or the raw
+    JSON values of a poll batch as (buf, off, ts) for process_json (decoded on
+    the GPU with device_decode), or None.
     `table` is a Table, or a Stream (the scalar SELECT chain)."""
     wm = -1  # tcTimestamp starts at -1 (Processor/Internal.hs:151)
     polls = 0
@@ -714,7 +745,10 @@ def runTask(poll, table: Table, max_polls=None, sink=None):
         batch = poll()
         if batch is None:
             break
-        wm, rows = table.process(batch, watermark=wm)
+        if isinstance(batch, tuple):
+            wm, rows = table.process_json(*batch, watermark=wm, device_decode=device_decode)
+        else:
+            wm, rows = table.process(batch, watermark=wm)
         if sink is not None:
             for r in rows:
                 sink(r)

@@ -171,6 +171,104 @@ int  hsg_decode_json_batch(hsg_decoder *dec, hsg_keydict *dict, uint64_t n, cons
                            const int64_t *rec_ts, hsg_decode_buffers *bufs, hsg_batch *out, uint8_t *status,
                            uint64_t *rejected, uint32_t *spell, int n_threads);
 
+/* ---- GPU ingest ------------------------------------------------------------------
+ * The decode of a poll batch on the device, for the records whose host answer
+ * the device can prove (the fast subset below), with every other record sent
+ * through the host decoder above, in record order. An accepted record's key is
+ * already in the dictionary, so it inserts nothing: ids, alternate spellings,
+ * status and the dictionary come out exactly as from hsg_decode_json_spelled
+ * over the same batches.
+ *
+ * The fast subset. A record is accepted iff
+ *   - it is ws { ws (member (ws , ws member)*)? ws } ws, ws = [ \t\n\r]*,
+ *     a member string ws : ws value, a string '"' bytes 0x20-0x7E other than
+ *     '"' and '\' '"' (no escapes), a value a JSON number, such a string, true,
+ *     false or null (no nested object or array anywhere), of at most
+ *     HSG_GPU_DEC_MAX_RECORD bytes;
+ *   - every number of a decoded field (the key field, a configured column) has
+ *     at most 19 integer and fraction digits together (its coefficient m, all
+ *     of them read as one integer) and at most 3 exponent digits; se is the
+ *     literal exponent minus the count of fraction digits;
+ *   - an HSG_F64 column's number has m <= 2^53 and -22 <= se <= 22 (the value
+ *     is then one correctly rounded IEEE operation on two exact doubles);
+ *   - an HSG_I64 column's number is integral and inside int64;
+ *   - a numeric column's field, where present, is a number; the last
+ *     occurrence of a repeated member counts, for the key and every column;
+ *   - the key field is present, a string of the key is at most
+ *     HSG_GPU_DEC_MAX_KEY bytes, and the key is in the device key table (a copy
+ *     of the dictionary's keys the subset can express, kept in HBM);
+ *   - with spellings asked for, a numeric key prints like the key's first
+ *     spelling.
+ * Anything else is a fallback record. */
+#define HSG_GPU_DEC_MAX_RECORD 4096u
+#define HSG_GPU_DEC_MAX_KEY 48u
+#define HSG_GPU_DEC_MAX_COLS 8
+#define HSG_GPU_DEC_MAX_NAME 64u
+
+/* The records' key spellings as the sink takes them (hstream_sink.h
+ * hsg_sink_encode_spelled, which says how they are read). */
+typedef struct {
+  const uint32_t *spell;
+  uint64_t n;
+  int64_t src_base;    /* global index of spell[0]'s record (the batch's first record) */
+  int32_t mem;         /* hsg_mem of spell */
+  int32_t reserved;
+} hsg_sink_spellings;
+
+typedef struct hsg_gpu_decoder hsg_gpu_decoder;
+typedef struct {
+  uint64_t records, accepted, host_records; /* this call                                  */
+  uint64_t new_keys;                        /* keys this call added to the dictionary      */
+  uint64_t table_slots, table_rebuilds;     /* the device key table: slots now, rebuilds
+                                               since the decoder was created               */
+} hsg_gpu_decode_stats;
+
+/* A device decoder over `dict` (NULL with key_field NULL) for batches of at
+ * most max_records records and max_bytes bytes; the key table starts at
+ * table_slots0 slots (rounded up to a power of two, at least 64) and grows by
+ * rebuild. HSG_E_INVALID for a configuration outside the device path (more
+ * than HSG_GPU_DEC_MAX_COLS columns, a field name longer than
+ * HSG_GPU_DEC_MAX_NAME bytes or with a byte outside the subset's string
+ * bytes): the caller keeps the host decoder. */
+int  hsg_gpu_decoder_create(hsg_engine *eng, const hsg_decoder_config *cfg, hsg_keydict *dict, uint64_t max_records,
+                            uint64_t max_bytes, uint64_t table_slots0, hsg_gpu_decoder **out);
+/* One poll batch (buf, off, rec_ts as hsg_decode_json; host memory). *out is an
+ * HSG_MEM_DEVICE batch at full width over arrays the decoder owns, ready_event
+ * recorded after the last write. The decoder alternates between two output
+ * sets: a batch stays valid until the call after the next one, so an
+ * asynchronous push of one batch overlaps the decode of the next. status and
+ * rejected (optional) are host-side, as hsg_decode_json_spelled's. want_spell:
+ * the records' spellings, in device memory, through *spell_out (src_base is
+ * left 0 for the caller). HSG_E_CAPACITY, with nothing changed, for n above
+ * max_records or more bytes than max_bytes. n_threads: the host decoder's, for
+ * the fallback records. */
+int  hsg_gpu_decode_json(hsg_gpu_decoder *dec, uint64_t n, const char *buf, const uint64_t *off, const int64_t *rec_ts,
+                         hsg_batch *out, uint8_t *status, uint64_t *rejected, int want_spell,
+                         hsg_sink_spellings *spell_out, hsg_gpu_decode_stats *stats, int n_threads);
+/* A batch of hsg_gpu_decode_json (and its spellings, sp may be NULL) copied to
+ * host arrays, after its ready_event; NULL arrays are skipped. For tests and
+ * hosts that inspect a batch; the pipeline itself pushes the device batch. */
+int  hsg_gpu_decoder_fetch(hsg_gpu_decoder *dec, const hsg_batch *b, const hsg_sink_spellings *sp, uint32_t *key_id,
+                           int64_t *ts, void *const *cols, uint8_t *const *valid, uint32_t *spell);
+void hsg_gpu_decoder_destroy(hsg_gpu_decoder *dec);
+const char *hsg_gpu_decoder_last_error(const hsg_gpu_decoder *dec);
+
+/* The fast subset's scanner on the host, one record (no key table: the
+ * key-independent part of the verdict). For tests and tools. */
+typedef struct {
+  int32_t accept;        /* 1: inside the subset (words / valid filled); 0: a fallback record */
+  int32_t key_tag;       /* 'n' number, 's' string, 'z' null, 't', 'f'; 0: no key member       */
+  int32_t key_neg;       /* a number key: sign, coefficient without trailing zeros, exponent   */
+  int32_t key_e;
+  uint64_t key_m;
+  uint32_t key_off, key_len; /* a string key: its span of the record                            */
+  int32_t key_int_form;  /* a number key: its literal prints as an integer (se >= 0)           */
+  int32_t reserved;
+  uint64_t words[8];
+  uint8_t valid[8];
+} hsg_json_probe;
+int  hsg_json_fast_probe(const hsg_decoder_config *cfg, const char *rec, uint64_t len, hsg_json_probe *out);
+
 #ifdef __cplusplus
 }
 #endif

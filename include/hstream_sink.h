@@ -81,13 +81,7 @@ int  hsg_sink_encode(hsg_sink *s, const hsg_rows *rows, uint64_t n, hsg_sink_rec
  * hsg_sink_encode_spelled: a row whose src_index is in [src_base, src_base + n)
  * prints its key as spell[src_index - src_base]; other rows (per-batch rows,
  * src_index -1) print the key's first spelling. */
-typedef struct {
-  const uint32_t *spell;
-  uint64_t n;
-  int64_t src_base;    /* global index of spell[0]'s record (the batch's first record) */
-  int32_t mem;         /* hsg_mem of spell */
-  int32_t reserved;
-} hsg_sink_spellings;
+/* (hsg_sink_spellings itself: hstream_ingest.h, whose device decoder fills one) */
 /* hsg_sink_encode with the records' key spellings (sp may be NULL); rows'
  * src_index is read when sp is given. */
 int  hsg_sink_encode_spelled(hsg_sink *s, const hsg_rows *rows, uint64_t n, const hsg_sink_spellings *sp,
